@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 512x512 images/sec at 50 DDIM steps (BASELINE.json metric), synthetic inputs.
 
-    python bench.py --gpus N --steps K --warmup W [--workload t2i|i2v|dual|triple]
+    python bench.py --gpus N --steps K --warmup W [--workload t2i|i2v|dual|triple] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself under torch.distributed.run with N
@@ -17,7 +17,12 @@ starts.  Every configuration goes through lib.model_zoo.sharded.vd_sample_sharde
 and sliced per rank, each rank samples its slice (per-GPU batch fixed: weak scaling), and the decoded images are
 all-gathered over RCCL inside the timed region.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line: images/s (`value`), `ms_per_step`, the build of
+the library and the whole-path rate derived from the timed steps.  --dump-outputs DIR writes the decoded images of the
+last timed step (what a caller of the timed path receives) as DIR/images.npy in float32; every input is seeded, so two
+runs with the same arguments see the same inputs and two builds can be compared output for output.
+
+With --full the JSON line also carries
   unet_forward_ms_per_ddim_step_bsB -- BASELINE metric (ii): one guided DDIM step replayed from the sampler's HIP graph
   roofline      -- for the kernel that dominates a UNet forward of the workload: algorithmic FLOPs of its launches /
                    their measured duration (events on the launch stream), against the dense fp16 MFMA peak of MI355X
@@ -376,6 +381,18 @@ def workload_inputs(wl, per_gpu, world, rank, device):
     return n_global, ctxs, images
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """The decoded images of the last timed step as float32 [B, 3, H, W].  Larger than DUMP_LIMIT_BYTES (a global batch
+    beyond the 1-GPU defaults): the first images of the batch that fit."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_image = img[0].numel() * 4
+    keep = max(1, min(img.shape[0], DUMP_LIMIT_BYTES // per_image))
+    np.save(os.path.join(out_dir, "images.npy"), img[:keep].float().cpu().numpy())
+
+
 def default_per_gpu(wl):
     # t2i / i2v: BASELINE quotes a per-GPU batch.  dual / triple: BASELINE quotes the GLOBAL batch of the 8-GPU job (16 / 32);
     # a rank always runs its share of that job (2 / 4 images), so on N GPUs the job is N/8 of the 8-GPU one: per-GPU work is
@@ -398,7 +415,11 @@ def main():
                     help="skip the other_workloads block (configs[2..4], 2 timed batches each) of the default t2i line")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="run only the cpu_baseline leg (VD_CPU_THREADS selects the pinned thread count) and print it")
-    ap.add_argument("--dump-kernel-table", default=None, help="write the per-kernel table of the roofline leg here")
+    ap.add_argument("--dump-kernel-table", default=None, help="write the per-kernel table of the roofline leg here (--full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the decoded images of the last timed step to DIR/images.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure metric (ii), the roofline, the CPU baseline, the box calibration and the other workloads")
     args = ap.parse_args()
     wl = WORKLOADS[args.workload]
 
@@ -444,6 +465,9 @@ def main():
     px = 8 * wl["side"]
     assert img.shape == (n_global, 3, px, px) and bool(torch.isfinite(img).all())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
+
     ms_per_step = 1e3 * elapsed / args.steps
     value = n_global * args.steps / elapsed
     n_unet_steps = int(args.ddim_steps * (1 - FIDELITY)) if wl["vae_enc"] else args.ddim_steps
@@ -476,7 +500,7 @@ def main():
         out["algorithmic_tflop_per_step"] = round(alg_tf, 1)
         out["whole_path_tflops_per_gpu"] = round(alg_tf / (ms_per_step / 1e3), 1)
         out["whole_path_frac_of_mfma_peak"] = round(alg_tf / (ms_per_step / 1e3) / MFMA_FP16_PEAK_TFLOPS, 4)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # BASELINE metric (ii): device time of one guided DDIM step (UNet forward at CFG batch 2B + update) replayed
             # from the sampler's HIP graph; 40 % of the MFMA peak <=> 2 * B * gf_fwd / 1 PFLOP/s
             ms = graph_step_ms(net, sampler, wl, per_gpu, args.ddim_steps, device)
@@ -489,20 +513,21 @@ def main():
             if args.dump_kernel_table:
                 with open(args.dump_kernel_table, "w") as f:
                     json.dump(table, f, indent=1, sort_keys=True)
-        if not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_leg(net, device)
-        try:
-            out["box_calibration"] = box_calibration(device)
-            cal = out["box_calibration"]
-            if "unet_forward_ms_per_ddim_step_bs%d" % per_gpu in out and cal.get("ratio_to_r06_evidence_box", {}).get("gemm_8192_tflops"):
-                # the forward is MFMA-side work: its time on the evidence box's clock
-                out["unet_forward_ms_normalised_to_r06_box"] = round(
-                    out["unet_forward_ms_per_ddim_step_bs%d" % per_gpu] * cal["ratio_to_r06_evidence_box"]["gemm_8192_tflops"], 3)
-        except Exception as e:   # never lose the line over the calibration leg
-            out["box_calibration"] = {"error": str(e)}
-    if world == 1 and args.workload == "t2i" and args.batch is None and not args.no_other_workloads:
-        # BASELINE configs[2..4] on this GPU, after (and outside) the headline's timed region: the driver only ever runs the
-        # default command, this block gives those configurations a driver-run number as well
+        if args.full:
+            try:
+                out["box_calibration"] = box_calibration(device)
+                cal = out["box_calibration"]
+                if "unet_forward_ms_per_ddim_step_bs%d" % per_gpu in out and cal.get("ratio_to_r06_evidence_box", {}).get("gemm_8192_tflops"):
+                    # the forward is MFMA-side work: its time on the evidence box's clock
+                    out["unet_forward_ms_normalised_to_r06_box"] = round(
+                        out["unet_forward_ms_per_ddim_step_bs%d" % per_gpu] * cal["ratio_to_r06_evidence_box"]["gemm_8192_tflops"], 3)
+            except Exception as e:   # never lose the line over the calibration leg
+                out["box_calibration"] = {"error": str(e)}
+    if args.full and world == 1 and args.workload == "t2i" and args.batch is None and not args.no_other_workloads:
+        # BASELINE configs[2..4] on this GPU, after (and outside) the headline's timed region: a --full run gives those
+        # configurations a number from the same command as well
         others = {}
         del ctxs, images, img
         for name in ("i2v", "dual", "triple"):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from vdtest_util import GOLD, load_gold, meta, tiny_vd_cfg
+from vdtest_util import GOLD, SCHEDULE_GRID, STATE_DICT_MODELS, exact_digest, load_gold, load_ref_json, meta, tiny_vd_cfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("VD_QUIET", "1")
@@ -67,40 +67,31 @@ def test_model_cfg_bank_resolves_four_flow():
     assert dict(cfg.args.vae_cfg_list)["text"].type == "optimus_vae_next"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs/model"), reason="reference checkout not present")
-def test_reference_yaml_files_load_unchanged(monkeypatch):
-    """The reference's own configs/model/*.yaml resolve to the same model definitions through our bank."""
+def test_reference_yaml_files_load_unchanged():
+    """vd_four_flow_v1-0 as the reference's bank resolved it from its own configs/model/*.yaml (tests/golden/ref_cfg.json.gz)
+    and as our bank resolves it: the same model definitions."""
     from lib.cfg_helper import model_cfg_bank
     mine = model_cfg_bank()("vd_four_flow_v1-0")
-    monkeypatch.setenv("VD_CONFIG_DIR", "/root/reference/configs/model")
-    ref = model_cfg_bank()("vd_four_flow_v1-0")
+    ref = load_ref_json("ref_cfg.json.gz")["vd_four_flow_v1-0"]
     for key in ("diffuser_cfg_list", "ctx_cfg_list"):
-        for (n1, c1), (n2, c2) in zip(mine.args[key], ref.args[key]):
-            assert n1 == n2 and c1.type == c2.type
-            assert json.dumps(c1.args, sort_keys=True) == json.dumps(c2.args, sort_keys=True)
-    v1, v2 = dict(mine.args.vae_cfg_list)["image"], dict(ref.args.vae_cfg_list)["image"]
-    assert json.dumps(v1.args, sort_keys=True) == json.dumps(v2.args, sort_keys=True)
+        assert len(mine.args[key]) == len(ref["args"][key])
+        for (n1, c1), (n2, c2) in zip(mine.args[key], ref["args"][key]):
+            assert n1 == n2 and c1.type == c2["type"]
+            assert json.dumps(c1.args, sort_keys=True) == json.dumps(c2["args"], sort_keys=True)
+    v1, v2 = dict(mine.args.vae_cfg_list)["image"], dict(ref["args"]["vae_cfg_list"])["image"]
+    assert json.dumps(v1.args, sort_keys=True) == json.dumps(v2["args"], sort_keys=True)
     for k in ("beta_linear_start", "beta_linear_end", "timesteps", "global_layer_ptr"):
-        assert mine.args[k] == ref.args[k]
+        assert mine.args[k] == ref["args"][k]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs/model"), reason="reference checkout not present")
 def test_every_model_name_resolves_like_the_reference_bank():
     """All 27 model names of the reference's configs/model/*.yaml, resolved by the REFERENCE's own model_cfg_bank from its
-    own files (separate process, oracle/ref_cfg_dump.py) and by this package's bank from this package's YAML files:
-    identical resolved trees (type, args after super_cfg merging, MODEL() expansion, pth / hfm sources)."""
-    import subprocess
-    import sys
-    import yaml
+    own files (oracle/ref_cfg_dump.py, stored in tests/golden/ref_cfg.json.gz) and by this package's bank from this package's
+    YAML files: identical resolved trees (type, args after super_cfg merging, MODEL() expansion, pth / hfm sources)."""
     from lib.cfg_helper import model_cfg_bank
-    names = []
-    for fn in sorted(os.listdir("/root/reference/configs/model")):
-        if fn.endswith(".yaml"):
-            names += list(yaml.safe_load(open(os.path.join("/root/reference/configs/model", fn))))
+    ref = load_ref_json("ref_cfg.json.gz")
+    names = sorted(ref)
     assert len(names) == 27
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "ref_cfg_dump.py")] + names, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("{"):])
 
     def plain(o):
         if isinstance(o, dict):
@@ -114,20 +105,16 @@ def test_every_model_name_resolves_like_the_reference_bank():
         assert mine == ref[name], name
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib/model_zoo"), reason="reference checkout not present")
 def test_full_size_state_dict_layouts_equal_the_reference_modules():
     """FULL-size modules of the checkpoint (2-D UNet, 0-D UNet with data+context / context-only blocks, KL-f8 VAE, Optimus
-    BERT encoder and GPT-2 decoder), built on the meta device by the REFERENCE's registry from its own configs (separate
-    process, oracle/ref_state_dict_dump.py) and by this package: same state-dict keys, same shapes -- what loading
-    vd-four-flow-v1-0[-fp16].pth / kl-f8.pth / optimus-vae.pth relies on."""
-    import subprocess
-    import sys
+    BERT encoder and GPT-2 decoder), built on the meta device by the REFERENCE's registry from its own configs
+    (oracle/ref_state_dict_dump.py, stored in tests/golden/ref_state_dict_layouts.json.gz) and by this package: same
+    state-dict keys, same shapes -- what loading vd-four-flow-v1-0[-fp16].pth / kl-f8.pth / optimus-vae.pth relies on."""
     from lib.cfg_helper import model_cfg_bank
     from lib.model_zoo import get_model
-    names = ["openai_unet_2d_v1", "openai_unet_0d_v1_dc", "openai_unet_0d_v1_c", "autokl_v1", "optimus_bert_encoder", "optimus_gpt2_decoder"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "ref_state_dict_dump.py")] + names, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index('{"'):])
+    names = STATE_DICT_MODELS
+    ref = load_ref_json("ref_state_dict_layouts.json.gz")
+    assert sorted(ref) == sorted(names)
     for name in names:
         cfg = model_cfg_bank()(name)
         for k in ("pth", "ckpt", "hfm"):
@@ -139,37 +126,24 @@ def test_full_size_state_dict_layouts_equal_the_reference_modules():
     assert len(ref["openai_unet_2d_v1"]) == 686
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib/model_zoo"), reason="reference checkout not present")
 def test_schedule_helpers_bit_exact_against_live_reference_over_a_grid():
     """make_beta_schedule / make_ddim_timesteps / make_ddim_sampling_parameters of this package against the REFERENCE's own
-    functions (separate process, oracle/ref_schedules.py): every DDIM step count 1..120 plus 200 / 250 / 500 / 1000, both
+    functions (oracle/ref_schedules.py, stored in tests/golden/ref_schedules*): every DDIM step count 1..120 plus 200 / 250 / 500 / 1000, both
     discretisations, eta in {0, 0.25, 1}, the reference fed its model's fp32 alphas_cumprod buffer as its sampler does.
     Betas, timesteps, alphas and alphas_prev bit-exact; sigmas (eta > 0 only) to 2e-5 relative: the reference evaluates
     that one formula on a mix of an fp32 torch tensor and float64 numpy arrays whose promotion even depends on the array
-    length, this package evaluates it in float64; the same exception type where the reference raises."""
-    import subprocess
-    import sys
+    length, this package evaluates it in float64; the same exception type where the reference raises.  The bit-exact
+    arrays of one step count are stored as one SHA-256 over their dtypes, shapes and bytes (vdtest_util.exact_digest)."""
     from lib.model_zoo import diffusion_utils as du
-    grid = {"steps": list(range(1, 121)) + [200, 250, 500, 1000], "etas": [0.0, 0.25, 1.0], "methods": ["uniform", "quad"],
-            "schedules": [["linear", 1000, 0.00085, 0.012], ["linear", 1000, 1e-4, 2e-2], ["linear", 250, 0.0015, 0.0195],
-                          ["cosine", 1000, 1e-4, 2e-2], ["sqrt_linear", 1000, 1e-4, 2e-2], ["sqrt", 1000, 1e-4, 2e-2]]}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "ref_schedules.py")], input=json.dumps(grid),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index('{"'):])
-
-    def same(mine, e, what):
-        a = np.asarray(mine)
-        assert str(a.dtype) == e["dtype"] and list(a.shape) == e["shape"] and a.tobytes().hex() == e["hex"], what
+    grid = SCHEDULE_GRID
+    ref = load_ref_json("ref_schedules.json.gz")
+    sigmas = np.load(os.path.join(ROOT, "tests", "golden", "ref_schedules_sigmas.npz"))
 
     for name, n, a, b in grid["schedules"]:
         key = "%s/%d/%r/%r" % (name, n, a, b)
-        same(np.asarray(du.make_beta_schedule(name, n, linear_start=a, linear_end=b)), ref["betas"][key], key)
+        assert exact_digest([du.make_beta_schedule(name, n, linear_start=a, linear_end=b)]) == ref["betas"][key], key
     betas = np.asarray(du.make_beta_schedule("linear", 1000, linear_start=0.00085, linear_end=0.012))
     alphacums = np.cumprod(1.0 - betas, axis=0).astype(np.float32)
-
-    def dec(e):
-        return np.frombuffer(bytes.fromhex(e["hex"]), dtype=e["dtype"]).reshape(e["shape"])
 
     for method in grid["methods"]:
         for s_ in grid["steps"]:
@@ -180,18 +154,17 @@ def test_schedule_helpers_bit_exact_against_live_reference_over_a_grid():
                 assert type(ei.value).__name__ == e["error"], (method, s_)
                 continue
             ts = du.make_ddim_timesteps(method, s_, 1000, verbose=False)
-            same(ts, e["timesteps"], (method, s_))
+            exact = [ts]
             for eta in grid["etas"]:
-                ee = e["eta%r" % eta]
-                if isinstance(ee, dict):
+                if "eta%r" % eta in e["errors"]:
                     with pytest.raises(Exception) as ei:
                         du.make_ddim_sampling_parameters(alphacums, ts, eta, verbose=False)
-                    assert type(ei.value).__name__ == ee["error"], (method, s_, eta)
+                    assert type(ei.value).__name__ == e["errors"]["eta%r" % eta], (method, s_, eta)
                     continue
                 sig, al, alp = du.make_ddim_sampling_parameters(alphacums, ts, eta, verbose=False)
-                same(al, ee[1], (method, s_, eta, "alpha"))
-                same(alp, ee[2], (method, s_, eta, "alpha_prev"))
-                assert np.allclose(sig, dec(ee[0]), rtol=2e-5 if s_ > 1 else 2e-3, atol=0), (method, s_, eta, "sigma")
+                exact += [al, alp]
+                assert np.allclose(sig, sigmas["%s/%d/eta%r" % (method, s_, eta)], rtol=2e-5 if s_ > 1 else 2e-3, atol=0), (method, s_, eta, "sigma")
+            assert exact_digest(exact) == e["sha256"], (method, s_, "timesteps / alphas / alphas_prev")
 
 
 def test_state_dict_layout_matches_reference():

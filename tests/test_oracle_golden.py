@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import synth, vd_oracle as O
+from vdtest_util import fullwidth_inputs, live_case_inputs, load_ref_json, published_vocab_files, random_tokenizer_texts
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -224,15 +225,14 @@ def test_optimus_gpt2_oracle_vs_reference_fixture():
     assert net.lm_head.weight is net.transformer.wte.weight
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/model_zoo/optimus_models/vocab/gpt2-vocab.json"),
-                    reason="GPT-2 vocabulary files live in the reference checkout")
-def test_gpt2_tokenizer_matches_reference():
+def test_gpt2_tokenizer_matches_reference(tmp_path):
     """The product's GPT-2 byte-level BPE (lib/model_zoo/optimus.py) against ids / decoded strings the reference's
-    vendored tokenizer produced (tests/golden/optimus_tokenizer.json)."""
+    vendored tokenizer produced (tests/golden/optimus_tokenizer.json), with the published vocabulary and merges restricted
+    to the entries those strings use (vdtest_util.published_vocab_files)."""
     from lib.model_zoo.optimus import optimus_gpt2_tokenizer
     tk = json.load(open(os.path.join(GOLD, "optimus_tokenizer.json")))["tokenizer"]
-    v = "/root/reference/lib/model_zoo/optimus_models/vocab/"
-    tok = optimus_gpt2_tokenizer(vocab_file=v + "gpt2-vocab.json", merges_file=v + "gpt2-merges.txt")
+    vocab, merges, _ = published_vocab_files(tmp_path)
+    tok = optimus_gpt2_tokenizer(vocab_file=vocab, merges_file=merges)
     tok.add_special_tokens({"pad_token": "<PAD>", "bos_token": "<BOS>", "eos_token": "<EOS>"})
     assert [tok.encode("<BOS>"), tok.encode("<EOS>"), tok.encode("<PAD>")] == tk["special"] and len(tok) == tk["len"]
     for c in tk["cases"]:
@@ -292,12 +292,10 @@ def test_bert_oracle_vs_reference_fixture():
 def test_bert_tokenizer_matches_reference(full, tmp_path):
     """The product's BERT basic + WordPiece tokenizer against pieces / ids the reference's vendored BertTokenizer produced
     (cased and lower-casing variants, accents, CJK, punctuation runs, an over-long word, a special token inside the text);
-    with the published vocabulary when the reference checkout is present, and always with the reduced one."""
+    with the published vocabulary restricted to the pieces of every tokenizer fixture (vdtest_util.published_vocab_files,
+    cased and lower-casing cases), and with the reduced one built from the cased cases alone."""
     from lib.model_zoo.optimus import optimus_bert_tokenizer
-    published = "/root/reference/lib/model_zoo/optimus_models/vocab/bert-base-cased-vocab.txt"
-    if full and not os.path.exists(published):
-        pytest.skip("published BERT vocabulary lives in the reference checkout")
-    vocab = published if full else reduced_bert_vocab(str(tmp_path / "vocab.txt"))
+    vocab = published_vocab_files(tmp_path)[2] if full else reduced_bert_vocab(str(tmp_path / "vocab.txt"))
     tk = _bert_meta()["tokenizer"]
     tok = optimus_bert_tokenizer(vocab_file=vocab, do_lower_case=False, max_len=512)
     assert [tok.cls_token_id, tok.sep_token_id, tok.pad_token_id, tok.unk_token_id] == tk["special"] and len(tok) == tk["len"]
@@ -334,38 +332,17 @@ def test_top_k_top_p_filter_equals_reference_rule(top_k, top_p):
         assert torch.allclose(p, ref, rtol=1e-5, atol=1e-8)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/model_zoo/optimus_models/vocab/gpt2-vocab.json"),
-                    reason="reference checkout (tokenizers + published vocabularies) not present")
-def test_tokenizers_against_live_reference_on_random_strings():
+def test_tokenizers_against_live_reference_on_random_strings(tmp_path):
     """300 seeded random strings (ASCII words, digits, punctuation runs, accents, CJK, emoji, odd whitespace, control
-    characters, contractions) through the REFERENCE's own BERT and GPT-2 tokenizers (separate process,
-    oracle/ref_tokenize.py) and through the product's re-implementations: identical pieces / ids / decoded text."""
-    import random
-    import subprocess
-    import sys
+    characters, contractions) through the REFERENCE's own BERT and GPT-2 tokenizers (oracle/ref_tokenize.py, stored in
+    tests/golden/ref_tokenize.json.gz) and through the product's re-implementations: identical pieces / ids / decoded text."""
     from lib.model_zoo.optimus import optimus_bert_tokenizer, optimus_gpt2_tokenizer
-    rnd = random.Random(20260924)
-    words = ["the", "a", "Photo", "of", "cat", "sitting", "don't", "it's", "I'm", "we've", "they're", "can not", "do not",
-             "unaffable", "naïve", "café", "São", "Zürich", "山", "水", "画", "日本語", "☕", "🙂", "12:30", "3.14", "#42", "e-mail",
-             "U.S.A.", "o'keeffe", "(oil)", "[x]", "{y}", "a/b", "50%", "$5", "x_y", "--", "...", "?!", "\t", "\n", "\u00a0", "\u2009",
-             "\x07", "\ufffd", "Ωmega", "straße", "İstanbul", "supercalifragilisticexpialidocious", "aaaaaaaaaa" * 11]
-    seps = [" ", " ", " ", "  ", ", ", ". ", "! ", "\t", "\n", "", "-", "' "]
-    texts = []
-    for _ in range(300):
-        n = rnd.randint(1, 9)
-        t = ""
-        for _ in range(n):
-            t += rnd.choice(words) + rnd.choice(seps)
-        texts.append(t.strip() if rnd.random() < 0.5 else t)
-    texts += ["", " ", "a", "A", ".", "hello world", "Hello, World!"]
-    texts = [t for t in texts if t.strip()]        # whitespace-only input: documented difference (reference emits a random special token)
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "ref_tokenize.py")], input=json.dumps(texts),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    ref = json.loads(r.stdout[r.stdout.index("{"):])
-    v = "/root/reference/lib/model_zoo/optimus_models/vocab/"
-    bert = optimus_bert_tokenizer(vocab_file=v + "bert-base-cased-vocab.txt", do_lower_case=False, max_len=512)
-    gpt2 = optimus_gpt2_tokenizer(vocab_file=v + "gpt2-vocab.json", merges_file=v + "gpt2-merges.txt")
+    texts = random_tokenizer_texts()
+    ref = load_ref_json("ref_tokenize.json.gz")
+    assert ref["texts"] == texts
+    gv, gm, bv = published_vocab_files(tmp_path)
+    bert = optimus_bert_tokenizer(vocab_file=bv, do_lower_case=False, max_len=512)
+    gpt2 = optimus_gpt2_tokenizer(vocab_file=gv, merges_file=gm)
     gpt2.add_special_tokens({"pad_token": "<PAD>", "bos_token": "<BOS>", "eos_token": "<EOS>"})
     bad = []
     for i, t in enumerate(texts):
@@ -379,24 +356,18 @@ def test_tokenizers_against_live_reference_on_random_strings():
     assert not bad, bad[:3]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib/model_zoo"), reason="reference checkout not present")
-def test_oracle_against_live_reference_on_random_cases(tiny_sd, meta, tmp_path):
+def test_oracle_against_live_reference_on_random_cases(tiny_sd, meta):
     """Beyond the fixed fixtures: 8 seeded random cases (batch 1-3, 8/16/24-pixel ragged latents, context lengths 3-89,
     random timesteps, mixing ratios, guidance scales, step counts; single-context, two-context and partial-schedule DDIM
-    loops; KL-f8 encode / decode at random image sizes; the text-latent flow) run through the LIVE reference in a separate process (oracle/ref_live_cases.py) and replayed through the
-    oracle: forwards < 1e-5, final latents < 1e-4 rel-L2."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "live.npz")
-    r = subprocess.run([sys.executable, os.path.join(root, "oracle", "ref_live_cases.py"), out, "20260924", "8"],
-                       capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = np.load(out)
+    loops; KL-f8 encode / decode at random image sizes; the text-latent flow) run through the LIVE reference (oracle/ref_live_cases.py, seed 20260924, stored in
+    tests/golden/ref_live_cases.npz, inputs drawn again from the seeds) and replayed through the oracle: forwards < 1e-5, final
+    latents < 1e-4 rel-L2."""
+    d = np.load(os.path.join(GOLD, "ref_live_cases.npz"))
     plan = O.unet_plan(**meta["unet2d"])
     flavours = set()
     for k in range(int(d["n"])):
-        g = lambda n: T(d["%d_%s" % (k, n)])
+        inp = live_case_inputs(d, k)
+        g = lambda n: inp[n] if n in inp else T(d["%d_%s" % (k, n)])
         ratio, steps, scale, flavour, fwd = [float(v) for v in d["%d_meta" % k]]
         x, t, ct, ci = g("x"), g("t").long(), g("ct"), g("ci")
         with torch.no_grad():
@@ -430,22 +401,17 @@ def test_oracle_against_live_reference_on_random_cases(tiny_sd, meta, tmp_path):
     assert flavours == {0, 1, 2}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib/model_zoo"), reason="reference checkout not present")
-def test_oracle_against_live_reference_at_full_width(tmp_path):
+def test_oracle_against_live_reference_at_full_width():
     """The oracle pinned at the width the GPU parity tests use it at: VD_v2_0 built by the REFERENCE's registry from its own
     YAML configs (openai_unet_2d_v1, 859.5 M parameters; openai_unet_0d_v1_dc, 1.71 B), synthetic weights regenerated by
-    name on both sides, 16x16 latent, L = 77 text / 257 image tokens (separate process, oracle/ref_live_fullwidth.py):
+    name on both sides, 16x16 latent, L = 77 text / 257 image tokens (oracle/ref_live_fullwidth.py, seed 7, stored in
+    tests/golden/ref_live_fullwidth.npz, inputs drawn again from the seeds):
     single-context and mixed-context forwards of the image flow, the text-latent (0-D) flow with either context, and a
     4-step guided DDIM loop replayed through the oracle: forwards < 2e-5, final latent < 1e-4 rel-L2."""
-    import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "fullwidth.npz")
     seed = 7
-    r = subprocess.run([sys.executable, os.path.join(root, "oracle", "ref_live_fullwidth.py"), out, str(seed)],
-                       capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = np.load(out)
+    d = np.load(os.path.join(GOLD, "ref_live_fullwidth.npz"))
     assert [int(v) for v in d["nparams"]] == [859520964, 1706797888]
     sys.path.insert(0, os.path.join(root, "versatile-diffusion_amd"))
     from lib.cfg_helper import CfgDict, model_cfg_bank
@@ -460,7 +426,8 @@ def test_oracle_against_live_reference_at_full_width(tmp_path):
         shapes = synth.shapes_of(get_model()(cfg, verbose=False))
     sd = synth.synth_state_dict(shapes, seed)
     sd.update(O.register_schedule())
-    g = lambda n: T(d[n])
+    inp = fullwidth_inputs()
+    g = lambda n: inp[n] if n in inp else T(d[n])
     x, t, ct, ci, x0d = g("x"), g("t").long(), g("ct"), g("ci"), g("x0d")
     p2, p0 = O.unet_plan(**dict(bank("openai_unet_2d_v1").args)), O.unet0d_plan(**dict(bank("openai_unet_0d_v1_dc").args))
     with torch.no_grad():
@@ -475,20 +442,12 @@ def test_oracle_against_live_reference_at_full_width(tmp_path):
         assert rel(z, g("z")) < 1e-4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib/model_zoo"), reason="reference checkout not present")
-def test_optimus_oracle_against_live_reference_on_random_cases(tmp_path):
+def test_optimus_oracle_against_live_reference_on_random_cases():
     """GPT-2 latent-connector logits (random sequence lengths 1-19, batches 1-3) and BERT latent-connector outputs (random
-    right-padded batches, lengths 2-29, incl. rows without padding) from the LIVE reference classes (separate process,
-    oracle/ref_live_optimus.py) against oracle/optimus_oracle.py."""
-    import subprocess
-    import sys
+    right-padded batches, lengths 2-29, incl. rows without padding) from the LIVE reference classes
+    (oracle/ref_live_optimus.py, seed 31, 6 cases, stored in tests/golden/ref_live_optimus.npz) against oracle/optimus_oracle.py."""
     from oracle import optimus_oracle as OO
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "lo.npz")
-    r = subprocess.run([sys.executable, os.path.join(root, "oracle", "ref_live_optimus.py"), out, "31", "6"],
-                       capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = np.load(out)
+    d = np.load(os.path.join(GOLD, "ref_live_optimus.npz"))
     meta_o, cfg, net, sd = _optimus_sd()
     mb = _bert_meta()
     from lib.model_zoo.optimus import optimus_bert_connector

@@ -60,3 +60,96 @@ def synth_into(net, seed):
     full = {k: v.detach().float().cpu() for k, v in net.state_dict().items()}
     full.update(sd)
     return full
+
+
+# ---- inputs of the differential tests against the reference (oracle/gen_golden_ref_dumps.py stores its outputs) ----
+STATE_DICT_MODELS = ["openai_unet_2d_v1", "openai_unet_0d_v1_dc", "openai_unet_0d_v1_c", "autokl_v1", "optimus_bert_encoder",
+                     "optimus_gpt2_decoder"]
+SCHEDULE_GRID = {"steps": list(range(1, 121)) + [200, 250, 500, 1000], "etas": [0.0, 0.25, 1.0], "methods": ["uniform", "quad"],
+                 "schedules": [["linear", 1000, 0.00085, 0.012], ["linear", 1000, 1e-4, 2e-2], ["linear", 250, 0.0015, 0.0195],
+                               ["cosine", 1000, 1e-4, 2e-2], ["sqrt_linear", 1000, 1e-4, 2e-2], ["sqrt", 1000, 1e-4, 2e-2]]}
+
+
+def random_tokenizer_texts():
+    """300 seeded random strings (ASCII words, digits, punctuation runs, accents, CJK, emoji, odd whitespace, control
+    characters, contractions) + a few edge cases; whitespace-only input dropped (documented difference)."""
+    import random
+    rnd = random.Random(20260924)
+    words = ["the", "a", "Photo", "of", "cat", "sitting", "don't", "it's", "I'm", "we've", "they're", "can not", "do not",
+             "unaffable", "naïve", "café", "São", "Zürich", "山", "水", "画", "日本語", "☕", "🙂", "12:30", "3.14", "#42", "e-mail",
+             "U.S.A.", "o'keeffe", "(oil)", "[x]", "{y}", "a/b", "50%", "$5", "x_y", "--", "...", "?!", "\t", "\n", "\u00a0", "\u2009",
+             "\x07", "\ufffd", "Ωmega", "straße", "İstanbul", "supercalifragilisticexpialidocious", "aaaaaaaaaa" * 11]
+    seps = [" ", " ", " ", "  ", ", ", ". ", "! ", "\t", "\n", "", "-", "' "]
+    texts = []
+    for _ in range(300):
+        n = rnd.randint(1, 9)
+        t = ""
+        for _ in range(n):
+            t += rnd.choice(words) + rnd.choice(seps)
+        texts.append(t.strip() if rnd.random() < 0.5 else t)
+    texts += ["", " ", "a", "A", ".", "hello world", "Hello, World!"]
+    return [t for t in texts if t.strip()]
+
+
+def published_vocab_files(tmp_dir):
+    """The published GPT-2 vocabulary / merges and BERT vocabulary restricted to the entries the tokenizer fixtures use
+    (tests/golden/optimus_vocab_subset.json.gz), every other id a placeholder: (gpt2 vocab, gpt2 merges, bert vocab) paths.
+    Same results on those texts as the full files: BPE applies the lowest-ranked merge present, and every merge it
+    applies is kept in its published order; WordPiece takes the longest piece present, and every piece it takes is kept."""
+    sub = load_ref_json("optimus_vocab_subset.json.gz")
+    g = sub["gpt2"]
+    vocab = {"[unused-%d]" % i: i for i in range(g["len"])}
+    for i in set(g["tokens"].values()) | {g["unk"][1]}:
+        vocab.pop("[unused-%d]" % i)
+    vocab.update(g["tokens"])
+    vocab[g["unk"][0]] = g["unk"][1]
+    assert len(vocab) == g["len"]
+    paths = [os.path.join(str(tmp_dir), n) for n in ("gpt2-vocab.json", "gpt2-merges.txt", "bert-base-cased-vocab.txt")]
+    with open(paths[0], "w", encoding="utf-8") as f:
+        json.dump(vocab, f, ensure_ascii=False)
+    with open(paths[1], "w", encoding="utf-8") as f:
+        f.write("#version: 0.2\n" + "\n".join(g["merges"]) + "\n")
+    b = sub["bert"]
+    lines = ["[unused-%d]" % i for i in range(b["len"])]
+    for piece, i in b["pieces"].items():
+        lines[i] = piece
+    with open(paths[2], "w", encoding="utf-8") as f:
+        f.write("\n".join(lines) + "\n")
+    return paths
+
+
+def live_case_inputs(d, k):
+    """Inputs of case k of oracle/ref_live_cases.py, drawn again from the seeds it uses (the fixture holds the reference's
+    outputs, the geometry and the timesteps only)."""
+    from oracle.gen_golden import seeded
+    B, H, W, Lt, Li, Hi, Wi = [int(v) for v in d["%d_dims" % k]]
+    return {"x": seeded((B, 4, H, W), 100 + k), "ct": seeded((B, Lt, 128), 200 + k, 0.5), "ci": seeded((B, Li, 128), 300 + k, 0.5),
+            "ut": seeded((1, Lt, 128), 400 + k, 0.5).repeat(B, 1, 1), "xT": seeded((B, 4, H, W), 500 + k),
+            "img": torch.rand((B, 3, Hi, Wi), generator=torch.Generator().manual_seed(600 + k)),
+            "zl": seeded((B, 4, Hi // 2, Wi // 2), 700 + k), "x0d": seeded((B, 128), 800 + k)}
+
+
+def fullwidth_inputs():
+    """Inputs of oracle/ref_live_fullwidth.py, drawn again from the seeds it uses."""
+    from oracle.gen_golden import seeded
+    B, H, W = 2, 16, 16
+    return {"x": seeded((B, 4, H, W), 1), "ct": seeded((B, 77, 768), 2, 0.5), "ci": seeded((B, 257, 768), 3, 0.5),
+            "x0d": seeded((B, 768), 4), "ut": seeded((1, 77, 768), 5, 0.5).repeat(B, 1, 1), "xT": seeded((B, 4, H, W), 6)}
+
+
+def exact_digest(arrays):
+    """SHA-256 over dtype, shape and bytes of each array in turn: what the schedule fixture stores for bit-exact arrays."""
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.asarray(a)
+        h.update(("%s%s" % (a.dtype, list(a.shape))).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def load_ref_json(name):
+    """A gzip-compressed JSON dump of the reference's own code (oracle/gen_golden_ref_dumps.py)."""
+    import gzip
+    with gzip.open(os.path.join(GOLD, name), "rt", encoding="utf-8") as f:
+        return json.load(f)

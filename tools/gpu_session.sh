@@ -40,7 +40,7 @@ for step in "$@"; do
         envrun "$benv" timeout 1500 python bench.py $(echo "$bargs" | tr ',' ' ') > $O/$tag.json 2> $O/$tag.err; echo "rc=$?"
         tail -1 $O/$tag.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print({k: d.get(k) for k in ('value','ms_per_step','unet_forward_ms_per_ddim_step_bs4','whole_path_frac_of_mfma_peak')}, {k: v.get('value') for k, v in (d.get('other_workloads') or {}).items()}, (d.get('roofline') or {}).get('frac'))" ;;
     trace)
-        (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o t -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads > $O/$tag.log 2>&1); echo "rc=$?"
+        (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o t -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads > $O/$tag.log 2>&1); echo "rc=$?"
         DB=$(find $O/prof_bench -name "*.db" | head -1)
         python tools/kernel_stats.py $DB > $O/kernel_stats.csv 2> $O/kernel_stats.err; head -12 $O/kernel_stats.csv | cut -c1-220
         NF=$(python tools/count_forwards.py $DB); echo "forwards in the traced run: $NF"

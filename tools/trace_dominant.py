@@ -30,4 +30,4 @@ for s, e, name in cur.execute("select start, end, %s from %s" % (nc, t[0])):
         n += 1
         tot += e - s
 print(json.dumps({"library_digest": lib_digest(), "kernel": want, "calls": n, "avg_us": round(tot / max(n, 1) / 1e3, 3),
-                  "command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads"}))
+                  "command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-workloads"}))
