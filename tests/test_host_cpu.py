@@ -211,6 +211,36 @@ def test_half_batch_fork_region_of_the_unet_walk():
     assert vd._fork_region(steps, 16 * 16, 256) is None       # a 16x16 latent never leaves the range again: no region
 
 
+def test_pack_build_counter():
+    """hip_layers.PackCache.builds, the process-wide count the forked branches of vd.run_unet order themselves by: it moves on a
+    cache miss, on the version change of an in-place edit and of load_state_dict, and stays still on a hit."""
+    from lib.model_zoo import vd
+    from lib.model_zoo.hip_layers import Conv2d, Linear, PackCache
+    assert vd.PackCache is PackCache
+    torch.manual_seed(0)
+    lin, conv = Linear(64, 32), Conv2d(64, 32, 3, padding=1)
+    n = PackCache.builds
+    w, b = lin._w()
+    assert PackCache.builds == n + 1 and w.dtype == torch.float16
+    assert lin._w()[0] is w and PackCache.builds == n + 1                  # hit
+    conv._w()
+    assert PackCache.builds == n + 2
+    conv._w()
+    assert PackCache.builds == n + 2
+    with torch.no_grad():
+        lin.weight.mul_(2.0)                                                 # same storage, new version
+    w2, _ = lin._w()
+    assert PackCache.builds == n + 3 and torch.equal(w2, lin.weight.detach().half()) and not torch.equal(w2, w)
+    lin._w()
+    assert PackCache.builds == n + 3
+    conv.load_state_dict({k: v + 1 for k, v in conv.state_dict().items()})  # copy_ into the parameters: versions move
+    conv._w()
+    assert PackCache.builds == n + 4
+    conv._w()
+    lin._w()
+    assert PackCache.builds == n + 4
+
+
 def test_full_unet_structure():
     """Block inventory of openai_unet_2d_v1 without allocating it."""
     from lib.cfg_helper import model_cfg_bank

@@ -4,11 +4,14 @@ and (2) the CPU fp32 oracle on full-width models.
 Tolerance: the path computes in fp16 with fp32 accumulation/statistics; BASELINE.json's north star bounds the
 final latents at <= 1e-2 relative L2 vs the fp32 reference.  Single forwards are held to 5e-3.
 """
+import threading
+
 import numpy as np
 import pytest
 import torch
 
-from vdtest_util import full_vd_cfg, load_gold, meta, rel_l2, synth_into, tiny_vd_cfg
+from vdtest_util import (clear_pack_caches, delayed_pack_builds, full_vd_cfg, load_gold, meta, rel_l2, synth_into, tiny_vd_cfg,
+                         unet_middle)
 
 pytestmark = pytest.mark.gpu
 
@@ -278,6 +281,101 @@ def test_half_batch_branches_match_the_unforked_forward(full, dev, monkeypatch):
     m1 = multi()
     monkeypatch.setattr(vd, "BATCH_FORK", "0")
     assert torch.equal(m1, multi())
+
+
+def test_half_batch_branches_after_an_in_place_weight_edit(full, dev, monkeypatch):
+    """The geometry above after an in-place edit of one 8x8-level convolution and the FeedForward output projection of the
+    middle block (their weight-stream packs): the main branch rebuilds the packs on its stream, and the side branch must
+    read the rebuilt ones (tests/test_streams_gpu.py has the tiny-model cases; weights restored afterwards)."""
+    from lib.model_zoo import vd
+    net, _ = full
+    g = torch.Generator().manual_seed(21)
+    x = (torch.randn((4, 4, 64, 64), generator=g)).half().to(dev)
+    c = (torch.randn((4, 77, 768), generator=g) * 0.5).half().to(dev)
+    t = torch.tensor([741, 741, 301, 301], device=dev)
+    fwd = lambda: net.apply_model({"type": "image", "x": x}, t, {"type": "text", "c": c}).float()
+    monkeypatch.setattr(vd, "BATCH_FORK", "0")
+    r0 = fwd()
+    assert torch.equal(r0, fwd()), "geometry not bit-reproducible run to run"
+    monkeypatch.setattr(vd, "BATCH_FORK", "1")
+    fwd()
+    rb, st = unet_middle(net.diffuser["image"])
+    ws = [rb.in_layers[2].weight, st.transformer_blocks[0].ff.net[2].weight]
+    saved = [w.detach().clone() for w in ws]
+    try:
+        with torch.no_grad():
+            ws[0].mul_(0.75)
+            ws[1].mul_(1.25)
+        with delayed_pack_builds() as amp:
+            first = fwd()
+        assert amp.builds > 0
+        second = fwd()
+        assert torch.equal(first, second)
+        clear_pack_caches(net)          # every pack rebuilt from the edited weights, unforked: the fresh-net reference
+        monkeypatch.setattr(vd, "BATCH_FORK", "0")
+        ref = fwd()
+        assert not torch.equal(ref, r0)
+        assert rel_l2(second, ref) < FWD_TOL
+    finally:
+        with torch.no_grad():
+            for w, s0 in zip(ws, saved):
+                w.copy_(s0)
+
+
+def test_two_threads_fork_onto_their_own_side_streams(full, dev, monkeypatch):
+    """Two threads, each running dual-context forwards (context types forked onto side streams) on a stream of its own once
+    the weights have been used: every output equals the same call run alone.  At this geometry the side branch's long-K
+    projections take split-K launches whose slabs live in a per-stream workspace, so threads that shared a side stream would
+    interleave slab writes and reduces."""
+    from lib.model_zoo import vd
+    from vd_hip import ops
+    net, _ = full
+    g = torch.Generator().manual_seed(23)
+    t = torch.tensor([741, 301], device=dev)
+    inputs = [[(torch.randn((2, 4, 32, 32), generator=g).half().to(dev), (torch.randn((2, 77, 768), generator=g) * 0.5).half().to(dev),
+                (torch.randn((2, 257, 768), generator=g) * 0.5).half().to(dev)) for _ in range(4)] for _ in range(2)]
+    fwd = lambda x, ct, ci: net.apply_model_multicontext({"type": "image", "x": x}, t, [
+        {"type": "text", "c": ct, "ratio": 0.5}, {"type": "image", "c": ci, "ratio": 0.5}]).float()
+    alone = [[fwd(*inp) for inp in per] for per in inputs]
+    assert torch.equal(alone[0][0], fwd(*inputs[0][0])), "geometry not bit-reproducible run to run"
+    torch.cuda.synchronize()
+    slabs = []
+    real_ws = ops.workspace
+
+    def workspace(nbytes, device, tag="ws"):
+        if tag == "gemm":   # split-K slabs (the reduce reads them back)
+            slabs.append((threading.get_ident(), torch.cuda.current_stream().cuda_stream))
+        return real_ws(nbytes, device, tag)
+    monkeypatch.setattr(ops, "workspace", workspace)
+    outs, sides, mains, idents, errors = [None, None], [None, None], [None, None], [None, None], []
+    start = threading.Barrier(2)
+
+    def worker(k):
+        try:
+            s = torch.cuda.Stream(device=dev)
+            with torch.cuda.stream(s):
+                idents[k], mains[k] = threading.get_ident(), s.cuda_stream
+                sides[k] = {st.cuda_stream for st in vd._side_streams(dev, 1)}
+                start.wait(timeout=60)
+                outs[k] = [fwd(*inp) for inp in inputs[k]]
+            s.synchronize()
+        except BaseException as e:   # re-raised in the test thread
+            errors.append(e)
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join(timeout=300)
+    assert not any(th.is_alive() for th in threads)
+    if errors:
+        raise errors[0]
+    differ = [(k, j) for k in range(2) for j in range(4) if not torch.equal(outs[k][j], alone[k][j])]
+    assert not sides[0] & sides[1], "both threads fork onto side stream(s) %s (outputs that differ from the lone run: %s)" % (
+        sides[0] & sides[1], differ)
+    assert not (sides[0] | sides[1]) & {mains[0], mains[1]}
+    for k in range(2):
+        assert any(tid == idents[k] and sid in sides[k] for tid, sid in slabs), "no split-K launch on thread %d's side stream" % k
+    assert not differ, differ
 
 
 def test_bench_shape_forward_vs_oracle(full, dev):

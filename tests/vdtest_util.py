@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure)."""
+import contextlib
 import json
 import os
 
@@ -60,6 +61,84 @@ def synth_into(net, seed):
     full = {k: v.detach().float().cpu() for k, v in net.state_dict().items()}
     full.update(sd)
     return full
+
+
+# ---- race amplifier of the stream-ordering tests -------------------------------------------------------------------------------
+_DELAY = {}
+
+
+def _elapsed_ms(fn):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def gpu_delay(target_ms=30.0):
+    """(fn, ms): fn enqueues a harmless kernel of about target_ms on the current stream (torch.cuda._sleep, a bounded spin),
+    calibrated once per process with CUDA events; ms is what the calibrated delay measured.  Asserts 20 <= ms <= 50, so a test
+    built on it cannot go vacuous."""
+    import torch
+    if "fn" not in _DELAY:
+        torch.cuda._sleep(1000)
+        cycles = [1 << 20]
+        fn = lambda: torch.cuda._sleep(cycles[0])
+        ms = _elapsed_ms(fn)
+        assert ms > 0.05, "torch.cuda._sleep does not spin on this device (%.4f ms)" % ms
+        for _ in range(2):   # linear in the cycle count; the second pass absorbs the launch overhead of the probe
+            cycles[0] = max(1, int(cycles[0] * target_ms / ms))
+            ms = _elapsed_ms(fn)
+        _DELAY.update(fn=fn, ms=ms)
+    assert 20.0 <= _DELAY["ms"] <= 50.0, "race amplifier delay measured %.2f ms" % _DELAY["ms"]
+    return _DELAY["fn"], _DELAY["ms"]
+
+
+class _Amp(object):
+    ms = 0.0
+    builds = 0
+
+
+@contextlib.contextmanager
+def delayed_pack_builds(target_ms=30.0):
+    """Race amplifier: while active, every weight-pack build (a cache miss of hip_layers.PackCache._packed) first enqueues a
+    ~target_ms kernel on the current stream.  A branch on another stream that reads a freshly built pack without waiting for
+    the building stream then reads allocated but unwritten memory -- wrong values on every run, never a fault (packs are
+    weights and biases: no kernel uses them as addresses or indices).  Yields a record with the measured delay (.ms) and the
+    number of delayed builds (.builds)."""
+    from lib.model_zoo import hip_layers
+    delay, ms = gpu_delay(target_ms)
+    real = hip_layers.PackCache._packed
+    amp = _Amp()
+    amp.ms = ms
+
+    def _packed(self, key, tensors, fn):
+        def slow():
+            amp.builds += 1
+            delay()
+            return fn()
+        return real(self, key, tensors, slow)
+
+    hip_layers.PackCache._packed = _packed
+    try:
+        yield amp
+    finally:
+        hip_layers.PackCache._packed = real
+
+
+def unet_middle(unet):
+    """(ResBlock, SpatialTransformer) of the middle block of a UNetModel2D_Next: the lowest level, inside the half-batch
+    fork region at every geometry that has one."""
+    d, c = unet.i_order.count("d"), unet.i_order.count("c")
+    return unet.data_blocks[d][0], unet.context_blocks[c][0]
+
+
+def clear_pack_caches(net):
+    for m in net.modules():
+        m.__dict__.pop("_vd_pack_cache", None)
 
 
 # ---- inputs of the differential tests against the reference (oracle/gen_golden_ref_dumps.py stores its outputs) ----

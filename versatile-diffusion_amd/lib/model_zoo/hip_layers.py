@@ -23,7 +23,13 @@ def _ver(t):
 
 class PackCache:
     """Mixin: cache of kernel-layout fp16 copies of parameters, rebuilt when the parameter storage changes
-    (load_state_dict, .half(), .to(device))."""
+    (load_state_dict, .half(), .to(device), an in-place edit).
+
+    `PackCache.builds` counts the builds of the whole process.  A pack is written by kernels on the stream current at the
+    build, so the forked branches of vd.run_unet sample the counter around each branch: a branch that built packs another
+    branch may read orders the later branches behind itself.  A device tensor built lazily during a forward goes through
+    `_packed` for that reason."""
+    builds = 0
 
     def _packed(self, key, tensors, fn):
         cache = self.__dict__.setdefault("_vd_pack_cache", {})
@@ -33,6 +39,7 @@ class PackCache:
             with torch.no_grad():
                 val = fn()
             cache[key] = (ver, val)
+            PackCache.builds += 1
             return val
         return hit[1]
 

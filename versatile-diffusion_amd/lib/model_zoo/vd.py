@@ -10,6 +10,7 @@ projections can be cached across DDIM steps (`c_info['kv_cache']`, set up by DDI
 from functools import partial
 
 import os
+import threading
 
 import numpy as np
 import numpy.random as npr
@@ -21,6 +22,7 @@ from vd_hip import ops
 from ..log_service import print_log
 from .common.get_model import get_model, register
 from .diffusion_utils import extract_into_tensor, make_beta_schedule, timestep_embedding
+from .hip_layers import PackCache
 
 symbol = "vd"
 
@@ -48,16 +50,56 @@ BATCH_FORK = os.environ.get("VD_BATCH_FORK", "auto")
 BATCH_FORK_HW = int(os.environ.get("VD_BATCH_FORK_HW", "256"))
 BATCH_FORK_MIN = int(os.environ.get("VD_BATCH_FORK_MIN", "16"))
 _SIDE = {}
+_SIDE_LOCK = threading.Lock()
 
 
 def _side_streams(device, n, kind="ctx"):
-    """Side streams of the forked context-type branches, one set per device for the whole process: the eager warm-up step and
-    the captured step use the same streams, so the per-stream workspaces of vd_hip.ops (keyed by stream) are allocated once,
-    outside any capture."""
-    lst = _SIDE.setdefault((kind, device.index), [])
-    while len(lst) < n:
-        lst.append(torch.cuda.Stream(device=device))
-    return lst[:n]
+    """Side streams of the forked branches, one set per (thread, device): the sampler's eager warm-up step and its captured
+    step run on one thread and use the same streams, so the per-stream workspaces of vd_hip.ops (keyed by stream) are
+    allocated once, outside any capture; two threads never put their branches -- and split-K slabs -- on one stream.
+    (torch hands out streams round-robin from a fixed pool: one another live thread forks onto is skipped.)"""
+    me = threading.get_ident()
+    with _SIDE_LOCK:
+        lst = _SIDE.get((kind, device.index, me), [])
+        if len(lst) < n:
+            alive = {t.ident for t in threading.enumerate()} | {me}
+            for k in [k for k in _SIDE if k[2] not in alive]:
+                del _SIDE[k]
+            _SIDE[(kind, device.index, me)] = lst
+            taken = {s.cuda_stream for k, l in _SIDE.items() if k[2] != me for s in l}
+            for _ in range(64):
+                if len(lst) >= n:
+                    break
+                s = torch.cuda.Stream(device=device)
+                if s.cuda_stream not in taken:
+                    lst.append(s)
+            if len(lst) < n:
+                raise RuntimeError("run_unet: no side stream left that no other thread forks onto")
+        return lst[:n]
+
+
+class _BranchOrder(object):
+    """Start order of forked branches (the context types of a block, the half-batch branches).  A later branch starts behind
+    the fork event, recorded on the caller's stream behind everything the branches read -- unless an earlier branch BUILT
+    weight packs (PackCache.builds moved during its host walk): their writes are on that branch's stream, and the other branch
+    may read them, so the later branches start behind an event recorded after that branch.  Forwards that build nothing
+    (every forward once the weights have been used, and any captured step) keep fully parallel branches."""
+
+    def __init__(self, main):
+        self.gate = torch.cuda.Event()
+        self.gate.record(main)
+
+    def enter(self, stream, first=False):
+        """In front of a branch's launches on `stream` (first: the branch on the fork's own stream); returns a token."""
+        if not first:
+            stream.wait_event(self.gate)
+        return PackCache.builds
+
+    def leave(self, stream, token):
+        """Behind the branch's launches."""
+        if PackCache.builds != token:
+            self.gate = torch.cuda.Event()
+            self.gate.record(stream)
 
 
 def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None):
@@ -132,20 +174,19 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
             return out
         main = torch.cuda.current_stream()
         sides = _side_streams(h.device, len(modules) - 1)
-        fork = torch.cuda.Event()
-        fork.record(main)
+        order = _BranchOrder(main)
         outs, done = [], []
         for i, (module, spec, kv, r) in enumerate(zip(modules, specs, kvs, rs)):
             st = main if i == 0 else sides[i - 1]
             prev = outs[-1] if outs else None
             prev_done = done[-1] if done else None
             with torch.cuda.stream(st):
-                if i > 0:
-                    st.wait_event(fork)
+                tok = order.enter(st, first=i == 0)
                 out = module(h, None, spec[1], kv=kv, alpha=float(r), res=prev,
                              sync=(None if prev_done is None else (lambda e=prev_done, s_=st: s_.wait_event(e))))
                 ev = torch.cuda.Event()
                 ev.record(st)
+                order.leave(st, tok)
             if i > 0:
                 out.record_stream(main)
                 st_ = getattr(out, "_vd_stats", None)   # ChanStats of the block output, written by the branch's last launch
@@ -168,7 +209,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     arena.begin(x.device)
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
-                              h, nb, shared, repeat, data_net.__dict__.setdefault("_vd_fork_warm", set()))
+                              h, nb, shared, repeat)
     finally:
         arena.end()
         data_net.__dict__["_vd_rowsum_need"] = arena.need
@@ -201,7 +242,7 @@ def _fork_region(steps, hw0, thr):
     return (a, b) if depth == 0 and any(st[0] == "c" for st in steps[a:b]) else None
 
 
-def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, warm):
+def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat):
     state = {"shared": shared}
 
     def walk(lo, hi, h, hs, sl=None):
@@ -252,25 +293,21 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
             for st in steps[a:b]:
                 if st[0] == "c":
                     prepare_context(st[1], st[2])
-            # (the FIRST forward of a geometry orders the side branch behind the whole main branch: weight packs are built lazily at
-            # first use, and a pack built by one branch would reach the other unsynchronised; both halves have the same shapes, so
-            # the main branch builds every pack the side branch needs)
-            key = (B,) + tuple(h.shape[1:]) + tuple(id(st[1][0]) for st in steps[a:b] if st[0] == "c")[:1]
-            first = key not in warm
-            warm.add(key)
+            # (weight packs are built lazily -- at first use, and again after a weight change or at a new embedding mode -- on the
+            # stream of the branch that meets them first: _BranchOrder starts the side branch behind the main branch then; both
+            # halves have the same shapes, so the main branch builds every pack the side branch needs)
             main = torch.cuda.current_stream()
             side = _side_streams(h.device, 1, kind="batch")[0]
-            fork = torch.cuda.Event()
-            if not first:
-                fork.record(main)
+            order = _BranchOrder(main)
+            tok = order.enter(main, first=True)
             h0 = walk(a, b, h[:B // 2], [], (0, B // 2))
-            if first:
-                fork.record(main)
+            order.leave(main, tok)
             with torch.cuda.stream(side):
-                side.wait_event(fork)
+                tok = order.enter(side)
                 h1 = walk(a, b, h[B // 2:], [], (B // 2, B))
                 done = torch.cuda.Event()
                 done.record(side)
+                order.leave(side, tok)
             h1.record_stream(main)
             main.wait_event(done)
             h = torch.cat([h0, h1], 0)
