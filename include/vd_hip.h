@@ -395,6 +395,15 @@ int vd_cfg_ddim_step_f16(const void* x, const void* eps, const void* noise, void
 int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0, int64_t n,
                              int guided, const float* coef, hipStream_t stream);
 
+/* Classifier-free-guidance combine + DPM-Solver++(2M) multistep update in one pass (fp32 math), step scalars in device
+ * memory: coef[8] = {guidance scale, 1/sqrt(a_t), sqrt(1 - a_t), sigma_next/sigma_t, c_d, w_cur, w_prev, 0}.
+ *   e = e_u + s (e_c - e_u); x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); D = w_cur x0 + w_prev x0_hist;
+ *   x_next = (sigma_next/sigma_t) x + c_d D; then x0_hist = x0 (fp32[n]) and pred_x0 = x0 (fp16, may be NULL).
+ * x0_hist is not read when w_prev == 0 (first-order steps).  x_next may alias x.  Lets one captured HIP graph of a
+ * solver step be replayed for every step, like vd_cfg_ddim_step_dev_f16. */
+int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
+                              int guided, const float* coef, hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

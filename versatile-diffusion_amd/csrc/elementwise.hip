@@ -90,6 +90,66 @@ __global__ void cfg_ddim_dev_kernel(const f16* x, const f16* eps, const f16* noi
     }
 }
 
+// CFG combine + DPM-Solver++(2M) multistep update, step scalars in device memory (one captured graph serves all steps):
+// coef = {guidance scale, 1/sqrt(a_t), sqrt(1 - a_t), sigma_next / sigma_t, c_d, w_cur, w_prev, 0}
+//   x0 = (x - sqrt(1-a_t) e) / sqrt(a_t);  D = w_cur x0 + w_prev x0_hist;  x_next = (sigma_next / sigma_t) x + c_d D
+// then x0_hist = x0 (fp32).  w_prev == 0 (first-order rows) never reads x0_hist: it is uninitialised on the first step of a
+// call.  x_next may alias x (each element is read and written by the same lane).  vec != 0: every pointer is 16-byte
+// aligned (the host checks), so elements [0, n/8*8) move as 8 x fp16 / 2 x float4 per lane; the rest take the scalar loop.
+__device__ __forceinline__ float dpmpp_elem(float x, float eu, float ec, float h, int guided, bool second, float s,
+                                            float rsqrt_at, float sqrt_1mat, float ratio, float c_d, float w_cur,
+                                            float w_prev, float& x0) {
+    const float e = guided ? eu + s * (ec - eu) : eu;
+    x0 = (x - sqrt_1mat * e) * rsqrt_at;
+    float d = w_cur * x0;
+    if (second) d += w_prev * h;
+    return ratio * x + c_d * d;
+}
+
+__global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_hist, f16* x_next, f16* pred_x0, size_t n,
+                                     int guided, int vec, const float* coef) {
+    const float s = coef[0], rsqrt_at = coef[1], sqrt_1mat = coef[2], ratio = coef[3], c_d = coef[4], w_cur = coef[5],
+                w_prev = coef[6];
+    const bool second = w_prev != 0.f;          // uniform over the grid
+    const f16* eps_c = eps + n;
+    const size_t nv = vec ? n / 8 : 0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+        U4H8 xv, eu, ec, xo, po;
+        xv.u = reinterpret_cast<const uint4*>(x)[i];
+        eu.u = reinterpret_cast<const uint4*>(eps)[i];
+        if (guided) ec.u = reinterpret_cast<const uint4*>(eps_c)[i];
+        float h[8], x0[8];
+        float4* hp = reinterpret_cast<float4*>(x0_hist) + 2 * i;
+        if (second) {
+            const float4 h0 = hp[0], h1 = hp[1];
+            h[0] = h0.x; h[1] = h0.y; h[2] = h0.z; h[3] = h0.w; h[4] = h1.x; h[5] = h1.y; h[6] = h1.z; h[7] = h1.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h[j] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float xn = dpmpp_elem((float)xv.e[j], (float)eu.e[j], guided ? (float)ec.e[j] : 0.f, h[j], guided, second,
+                                        s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0[j]);
+            xo.e[j] = (f16)xn;
+            po.e[j] = (f16)x0[j];
+        }
+        reinterpret_cast<uint4*>(x_next)[i] = xo.u;
+        hp[0] = make_float4(x0[0], x0[1], x0[2], x0[3]);
+        hp[1] = make_float4(x0[4], x0[5], x0[6], x0[7]);
+        if (pred_x0 != nullptr) reinterpret_cast<uint4*>(pred_x0)[i] = po.u;
+    }
+    for (size_t i = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float x0;
+        const float xn = dpmpp_elem((float)x[i], (float)eps[i], guided ? (float)eps_c[i] : 0.f, second ? x0_hist[i] : 0.f,
+                                    guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
+        x_next[i] = (f16)xn;
+        x0_hist[i] = x0;
+        if (pred_x0 != nullptr) pred_x0[i] = (f16)x0;
+    }
+}
+
 __global__ void q_sample_kernel(const f16* x0, const f16* noise, const float* sa, const float* sb, f16* out, int B,
                                 size_t per_batch) {
     const size_t n = (size_t)B * per_batch;
@@ -368,6 +428,19 @@ extern "C" int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const vo
     hipLaunchKernelGGL(cfg_ddim_dev_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
                        (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef);
     return vd_check_launch("vd_cfg_ddim_step_dev_f16");
+}
+
+extern "C" int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
+                                         int64_t n, int guided, const float* coef, hipStream_t stream) {
+    VD_REQUIRE(x && eps && x0_hist && x_next && coef && n > 0, "vd_cfg_dpmpp_step_dev_f16: bad arguments");
+    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    // torch slices can start anywhere: the 16-byte path only when every stream (both eps halves included) is aligned
+    const int vec = a16(x) && a16(eps) && (!guided || a16((const f16*)eps + n)) && a16(x0_hist) && a16(x_next) &&
+                    (pred_x0 == nullptr || a16(pred_x0));
+    const size_t work = vec ? (size_t)(n + 7) / 8 : (size_t)n;
+    hipLaunchKernelGGL(cfg_dpmpp_dev_kernel, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
+                       x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, vec, coef);
+    return vd_check_launch("vd_cfg_dpmpp_step_dev_f16");
 }
 
 extern "C" int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,

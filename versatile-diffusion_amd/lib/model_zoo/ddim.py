@@ -20,6 +20,11 @@ from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
 
 
 class DDIMSampler(object):
+    # hooks of the static step loop (_loop_static) for samplers that share it (dpm_solver.DPMSolverSampler): the width of
+    # the per-step device coefficient row, and whether every step draws its reference noise_like(x) from the generator
+    coef_width = 6
+    draws_step_noise = True
+
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
         self.model = model
@@ -152,7 +157,8 @@ class DDIMSampler(object):
         return x_info["x"], intermediates
 
     def _coef_table(self, total_steps, scale, device):
-        """[S, 6] fp32 device table of {scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma, sqrt(1-a_t)}."""
+        """[S, 6] fp32 device table of {scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma, sqrt(1-a_t)}; row i is
+        copied into the static coef buffer before step i (a sampler on this loop returns its own [S, coef_width] table)."""
         a_t = self.ddim_alphas[:total_steps].astype(np.float64)
         a_prev = self.ddim_alphas_prev[:total_steps].astype(np.float64)
         sig = self.ddim_sigmas[:total_steps].astype(np.float64)
@@ -184,9 +190,10 @@ class DDIMSampler(object):
             nb = (2 if guided else 1) * x.shape[0]
             st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
                   "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
-                  "coef": torch.empty((6,), device=x.device, dtype=torch.float32),
+                  "coef": torch.empty((self.coef_width,), device=x.device, dtype=torch.float32),
                   "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
                   "kv": [dict() for _ in c_info_list], "graph": None}
+            st.update(self._extra_static(x))
             self._static[key] = st
         else:
             self._static[key] = self._static.pop(key)          # most recently used last
@@ -205,11 +212,13 @@ class DDIMSampler(object):
             xs = x.clone()
             x_next, p0 = torch.empty_like(xs), torch.empty_like(xs)
             ts = torch.empty((nb,), device=dev, dtype=torch.long)
-            coef = torch.empty((6,), device=dev, dtype=torch.float32)
+            coef = torch.empty((self.coef_width,), device=dev, dtype=torch.float32)
+            bufs = dict(xs=xs, x_next=x_next, p0=p0, coef=coef, **self._extra_static(x))
             graph = None
             replay_first = False
         else:
             xs, x_next, p0, ts, coef, graph = st["xs"], st["x_next"], st["p0"], st["ts"], st["coef"], st["graph"]
+            bufs = st
             replay_first = False
             xs.copy_(x)
             for ci, cbuf, kv in zip(c_info_list, st["c"], st["kv"]):
@@ -254,15 +263,14 @@ class DDIMSampler(object):
                 eps = self.model.apply_model(xi, ts, c_info_list[0])
             else:
                 eps = self.model.apply_model_multicontext(xi, ts, c_info_list)
-            ops.cfg_ddim_step_dev(xs, eps.contiguous(), coef, guided=guided, x_prev=x_next, pred_x0=p0)
-            xs.copy_(x_next)
+            self._update_static(bufs, eps.contiguous(), guided)
 
         # RNG contract: the reference draws noise_like(x) = torch.randn_like(x) on every step even when sigma = 0
         # (ddim.py:167 / :294 there), so the device generator ends a sample() call advanced by one latent-sized draw per
         # step.  The draws are consumed here, up front, and the generator state is pinned to that point after the loop
         # (graph capture / replay bookkeeping must not leak into it), so code that keeps drawing from the default
         # generator after sample() sees the reference's stream.
-        for _ in range(total_steps):
+        for _ in range(total_steps if self.draws_step_noise else 0):
             torch.randn_like(xs)
         rng_after = torch.cuda.get_rng_state(dev)
         for i in range(total_steps):
@@ -293,6 +301,16 @@ class DDIMSampler(object):
                 intermediates["pred_x0"].append(p0.to(dtype).clone())
         torch.cuda.set_rng_state(rng_after, dev)
         return xs.clone() if st is not None else xs, p0.clone() if st is not None else p0
+
+    def _extra_static(self, x):
+        """Further step-loop buffers (name -> tensor) of a sampler built on this loop, kept with the step graph."""
+        return {}
+
+    def _update_static(self, bufs, eps, guided):
+        """The update at the end of a static step: reads bufs["xs"] (latent), eps and bufs["coef"], leaves the next latent in
+        bufs["xs"] and the data prediction in bufs["p0"].  Captured into the step graph with the UNet forward."""
+        ops.cfg_ddim_step_dev(bufs["xs"], eps, bufs["coef"], guided=guided, x_prev=bufs["x_next"], pred_x0=bufs["p0"])
+        bufs["xs"].copy_(bufs["x_next"])
 
     def _capture(self, body):
         try:

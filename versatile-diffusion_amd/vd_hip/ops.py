@@ -935,6 +935,24 @@ def cfg_ddim_step_dev(x, eps, coef, *, guided, x_prev, pred_x0=None, noise=None)
     return x_prev, pred_x0
 
 
+def cfg_dpmpp_step_dev(x, eps, coef, x0_hist, *, guided, x_next, pred_x0=None):
+    """CFG + DPM-Solver++(2M) update with the step scalars in a device fp32[8] tensor (dpm_solver.dpmpp_coef_table rows);
+    reads and rewrites the fp32 data-prediction history `x0_hist`, writes into caller-owned buffers (x_next may be x)."""
+    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x0_hist, "x0_hist", torch.float32)
+    _req(x_next, "x_next"); _req(pred_x0, "pred_x0")
+    n = x.numel()
+    if eps.numel() != (2 * n if guided else n):
+        raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
+    for t, name in ((x0_hist, "x0_hist"), (x_next, "x_next"), (pred_x0, "pred_x0")):
+        if t is not None and t.numel() != n:
+            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
+    if coef.numel() < 8:
+        raise VdHipError("coef has %d elements, expected 8" % coef.numel())
+    _check(lib().vd_cfg_dpmpp_step_dev_f16(_ptr(x), _ptr(eps), _ptr(x0_hist), _ptr(x_next), _ptr(pred_x0), n,
+                                           1 if guided else 0, _ptr(coef), _stream()))
+    return x_next, pred_x0
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1165,7 +1183,7 @@ def _guarded(fn):
 
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
-              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
