@@ -404,6 +404,14 @@ int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, 
 int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
                               int guided, const float* coef, hipStream_t stream);
 
+/* Masked blend of blended latent diffusion (inpainting; not in the reference), after a sampler step lands on a_prev:
+ *   out = m x + (1 - m) (ca x0 + cn noise),  coef[2] = {ca, cn} = {sqrt(a_prev), sqrt(1 - a_prev)} (or {1, 0} on the
+ *   last step) in device memory, fp32 math, one fp16 rounding.
+ * x, x0, noise, out: fp16 [B, C, HW]; mask: fp16 [Bm, HW], Bm = 1 or B, broadcast over channels (1 = regenerate,
+ * 0 = keep).  out may alias x.  Returns < 0 (vd_last_error) for null pointers, B, C or HW <= 0, or another Bm. */
+int vd_masked_blend_f16(const void* x, const void* x0, const void* noise, const void* mask, void* out, int B, int C,
+                        int64_t HW, int Bm, const float* coef, hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

@@ -150,6 +150,42 @@ __global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_his
     }
 }
 
+// Masked blend of blended latent diffusion (inpainting; not in the reference, whose masks only weight the CLIP image
+// context).  After a sampler step lands on a_prev, the known region is reset to the forward process of the original latent:
+//   t = ca x0 + cn noise;  out = m x + (1 - m) t       coef = {ca, cn} = {sqrt(a_prev), sqrt(1 - a_prev)}, or {1, 0}
+// fp32 math, one fp16 rounding; m = 1 returns x and m = 0 with {1, 0} returns x0 bit for bit.  x, x0, noise, out are
+// [B, C, HW]; mask is [Bm, HW] with Bm = 1 (broadcast over the batch) or B, broadcast over channels.  out may alias x
+// (each element is read and written by the same lane).  vec != 0: every pointer is 16-byte aligned and HW % 8 == 0 (the
+// host checks), so 8 consecutive elements share one (b, c) row and move as one 16-byte access per stream.
+__device__ __forceinline__ float blend_elem(float x, float x0, float nz, float m, float ca, float cn) {
+    const float t = ca * x0 + cn * nz;
+    return m * x + (1.f - m) * t;
+}
+
+__global__ void masked_blend_kernel(const f16* x, const f16* x0, const f16* noise, const f16* mask, f16* out, size_t n,
+                                    size_t chw, size_t hw, int mask_batch, int vec, const float* coef) {
+    const float ca = coef[0], cn = coef[1];
+    const size_t nv = vec ? n / 8 : 0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+        const size_t e = 8 * i;
+        const size_t mi = (mask_batch ? e / chw * hw : 0) + e % hw;
+        U4H8 xv, av, nvv, mv, o;
+        xv.u = reinterpret_cast<const uint4*>(x)[i];
+        av.u = reinterpret_cast<const uint4*>(x0)[i];
+        nvv.u = reinterpret_cast<const uint4*>(noise)[i];
+        mv.u = *reinterpret_cast<const uint4*>(mask + mi);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            o.e[j] = (f16)blend_elem((float)xv.e[j], (float)av.e[j], (float)nvv.e[j], (float)mv.e[j], ca, cn);
+        reinterpret_cast<uint4*>(out)[i] = o.u;
+    }
+    for (size_t i = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t mi = (mask_batch ? i / chw * hw : 0) + i % hw;
+        out[i] = (f16)blend_elem((float)x[i], (float)x0[i], (float)noise[i], (float)mask[mi], ca, cn);
+    }
+}
+
 __global__ void q_sample_kernel(const f16* x0, const f16* noise, const float* sa, const float* sb, f16* out, int B,
                                 size_t per_batch) {
     const size_t n = (size_t)B * per_batch;
@@ -441,6 +477,20 @@ extern "C" int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* 
     hipLaunchKernelGGL(cfg_dpmpp_dev_kernel, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
                        x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, vec, coef);
     return vd_check_launch("vd_cfg_dpmpp_step_dev_f16");
+}
+
+extern "C" int vd_masked_blend_f16(const void* x, const void* x0, const void* noise, const void* mask, void* out, int B,
+                                   int C, int64_t HW, int Bm, const float* coef, hipStream_t stream) {
+    VD_REQUIRE(x && x0 && noise && mask && out && coef && B > 0 && C > 0 && HW > 0, "vd_masked_blend_f16: bad arguments");
+    VD_REQUIRE(Bm == 1 || Bm == B, "vd_masked_blend_f16: mask batch %d must be 1 or B = %d", Bm, B);
+    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const int vec = HW % 8 == 0 && a16(x) && a16(x0) && a16(noise) && a16(mask) && a16(out);
+    const size_t n = (size_t)B * C * HW;
+    const size_t work = vec ? n / 8 : n;
+    hipLaunchKernelGGL(masked_blend_kernel, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x, (const f16*)x0,
+                       (const f16*)noise, (const f16*)mask, (f16*)out, n, (size_t)C * HW, (size_t)HW, Bm == B && B > 1,
+                       vec, coef);
+    return vd_check_launch("vd_masked_blend_f16");
 }
 
 extern "C" int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,

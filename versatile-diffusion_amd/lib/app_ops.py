@@ -1,6 +1,7 @@
 """Device versions of the tensor work the reference does in app.py around the model calls:
 the 'Simple' colour adjustment of image variation (app.py:373-379) and the `adjust_rank` focus control of the image
-context (app.py:48-127).  Same call signatures as there; the arithmetic runs in hand-written HIP kernels (vd_hip)."""
+context (app.py:48-127).  Same call signatures as there; the arithmetic runs in hand-written HIP kernels (vd_hip).
+`latent_mask` (not in the reference) turns a pixel inpainting mask into the latent mask of x_info["inpaint_mask"]."""
 import numpy as np
 import torch
 
@@ -16,6 +17,20 @@ def color_adjust_simple(imout, cx):
     dt = x.dtype
     out = ops.color_adjust(x.to(torch.float16).contiguous(), cx.to(device=x.device, dtype=torch.float16).contiguous()).to(dt)
     return list(out) if as_list else out
+
+
+def latent_mask(mask, mode="max", factor=8):
+    """Pixel inpainting mask [B or 1, 1, H, W] (1 = regenerate, 0 = keep; float or bool) -> fp32 latent mask
+    [B or 1, 1, H / factor, W / factor] for x_info["inpaint_mask"] (factor: the VAE's downsampling, 8 for kl-f8).
+    mode "max" regenerates every latent pixel that touches a masked pixel; "area" takes the masked fraction (a soft mask).
+    Runs once per call, off the step path, so plain torch pooling does it."""
+    if mode not in ("max", "area"):
+        raise ValueError("latent_mask: mode must be 'max' or 'area', got %r" % (mode,))
+    if mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[2] % factor or mask.shape[3] % factor:
+        raise ValueError("latent_mask: expected a [B or 1, 1, H, W] mask with H and W multiples of %d, got %s"
+                         % (factor, tuple(mask.shape)))
+    pool = torch.nn.functional.max_pool2d if mode == "max" else torch.nn.functional.avg_pool2d
+    return pool(mask.float(), factor)
 
 
 class adjust_rank(object):

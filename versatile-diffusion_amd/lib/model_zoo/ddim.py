@@ -19,6 +19,39 @@ from vd_hip import ops
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
 
 
+def inpaint_blend_table(alphas_cumprod, timesteps):
+    """fp32 [S, 2] rows {ca, cn} of the inpainting blend (ops.masked_blend) per DDIM index i, computed in float64: after
+    the step of index i lands on a_prev[i] (DDIM's alphas_prev, the DPM solver's a_next), the known region is reset to
+    ca x0 + cn noise with (ca, cn) = (sqrt(a_prev[i]), sqrt(1 - a_prev[i])) for i > 0 and (1, 0) for i = 0, so the last
+    step returns the known region as x0 itself."""
+    _, _, a_prev = make_ddim_sampling_parameters(alphas_cumprod, np.asarray(timesteps), 0.0, verbose=False)
+    a_prev = np.asarray(a_prev, dtype=np.float64)
+    tab = np.stack([np.sqrt(a_prev), np.sqrt(1.0 - a_prev)], axis=1)
+    tab[0] = (1.0, 0.0)
+    return tab.astype(np.float32)
+
+
+def _inpaint_args(x_info, shape):
+    """(mask, x0) of the inpainting extension keys of x_info, validated against the latent shape, or None without a
+    mask.  Runs before anything touches the device."""
+    mask = x_info.get("inpaint_mask")
+    if mask is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("inpaint_mask applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    x0 = x_info.get("x0")
+    if x0 is None:
+        raise ValueError("inpaint_mask needs x_info['x0'], the encoded image")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4 or tuple(x0.shape) != shape:
+        raise ValueError("inpainting: x0 has shape %s, expected the latent shape %s" % (tuple(x0.shape), shape))
+    if mask.dim() != 4 or mask.shape[1] != 1 or tuple(mask.shape[2:]) != shape[2:]:
+        raise ValueError("inpaint_mask has shape %s, expected [B or 1, 1, %d, %d]" % ((tuple(mask.shape),) + shape[2:]))
+    if mask.shape[0] not in (1, shape[0]):
+        raise ValueError("inpaint_mask has batch %d, expected 1 or %d" % (mask.shape[0], shape[0]))
+    return mask, x0
+
+
 class DDIMSampler(object):
     # hooks of the static step loop (_loop_static) for samplers that share it (dpm_solver.DPMSolverSampler): the width of
     # the per-step device coefficient row, and whether every step draws its reference noise_like(x) from the generator
@@ -102,21 +135,35 @@ class DDIMSampler(object):
             return self._ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single)
 
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
+        inpaint = _inpaint_args(x_info, shape)
         device = self.model.device
         dtype = c_info_list[0]["conditioning"].dtype
         bs = shape[0]
         timesteps = self.ddim_timesteps
+        blend_noise = x_info.get("x0_noise")
         if ("xt" in x_info) and (x_info["xt"] is not None):
             x_info["x"] = x_info["xt"].to(device=device, dtype=dtype)
-        elif ("x0" in x_info) and (x_info["x0"] is not None):
+        elif ("x0" in x_info) and (x_info["x0"] is not None) and (inpaint is None or
+                                                                  x_info.get("x0_forward_timesteps") is not None):
             x0 = x_info["x0"].to(device=device, dtype=dtype)
             k = x_info["x0_forward_timesteps"]
             ts = torch.full((bs,), int(timesteps[k]), device=device, dtype=torch.long)
             timesteps = timesteps[:k]
             # `x0_noise` (extension): inject the forward-process noise instead of drawing it, for reproducible runs
-            x_info["x"] = self.model.q_sample(x0, ts, noise=x_info.get("x0_noise"))
+            q_noise = x_info.get("x0_noise")
+            if inpaint is not None and q_noise is None:
+                # the draw q_sample would make (same generator use as the unmasked call); the blend reuses it
+                q_noise = blend_noise = torch.randn_like(x0)
+            x_info["x"] = self.model.q_sample(x0, ts, noise=q_noise)
         else:
             x_info["x"] = torch.randn(shape, device=device, dtype=dtype)
+        if inpaint is not None:
+            # blended latent diffusion: one fixed noise for the whole call (x0_noise, else the start q_sample's, else x_T)
+            mask, x0 = inpaint
+            f16 = dict(device=device, dtype=torch.float16)
+            inpaint = {"x0": x0.to(**f16).contiguous(), "mask": mask.to(**f16).contiguous(),
+                       "noise": (x_info["x"] if blend_noise is None else blend_noise).to(**f16).contiguous(),
+                       "table": torch.from_numpy(inpaint_blend_table(self.alphas_cumprod, timesteps)).to(device)}
 
         scale = c_info_list[0]["unconditional_guidance_scale"]
         for ci in c_info_list:
@@ -143,13 +190,15 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, pred_x0 = self._loop_static(x, x_info, c_info_list, time_range, total_steps, guided, scale, _single,
-                                           log_every_t, intermediates, dtype)
+                                           log_every_t, intermediates, dtype, inpaint)
         else:
             pred_x0 = None
             for i, step in enumerate(time_range):
                 index = total_steps - i - 1
                 x, pred_x0 = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                         noise_dropout=noise_dropout)
+                if inpaint is not None:
+                    ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
                     intermediates["pred_xt"].append(x.to(dtype))
                     intermediates["pred_x0"].append(pred_x0.to(dtype))
@@ -167,7 +216,7 @@ class DDIMSampler(object):
                         self.ddim_sqrt_one_minus_alphas[:total_steps].astype(np.float64)], axis=1)
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
-    def _static_state(self, x, x_info, c_info_list, guided, single):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None):
         """Buffers the captured step reads and writes, kept ACROSS sample() calls per (model weights, shapes, flow): a
         second call with the same geometry re-uses the instantiated HIP graph instead of capturing again (capture =
         one host-bound pass over ~400 launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  Everything
@@ -180,9 +229,12 @@ class DDIMSampler(object):
         # that swap storages collide)
         wv = hash(tuple((t.data_ptr(), t._version) for t in list(self.model.parameters()) + list(self.model.buffers())))
         # (emb_hoist is part of the key: a step graph captured with the hoisted time embedding reads st["embrow"], one captured
-        # without it computes the embedding inside the step -- replaying either under the other setting would be silently wrong)
+        # without it computes the embedding inside the step -- replaying either under the other setting would be silently wrong;
+        # so is inpainting with its mask batch: a graph captured with the blend reads the static x0 / noise / mask buffers)
+        mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
-               tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list))
+               tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
+               inpaint is not None, mask_batch)
         st = self._static.get(key)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
@@ -194,26 +246,32 @@ class DDIMSampler(object):
                   "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
                   "kv": [dict() for _ in c_info_list], "graph": None}
             st.update(self._extra_static(x))
+            if inpaint is not None:
+                st.update({k: torch.empty_like(inpaint[k]) for k in ("x0", "noise", "mask")},
+                          blend=torch.empty((2,), device=x.device, dtype=torch.float32))
             self._static[key] = st
         else:
             self._static[key] = self._static.pop(key)          # most recently used last
         return st
 
     def _loop_static(self, x, x_info, c_info_list, time_range, total_steps, guided, scale, single, log_every_t,
-                     intermediates, dtype):
+                     intermediates, dtype, inpaint=None):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry."""
         dev = x.device
         b = x.shape[0]
         nb = 2 * b if guided else b
-        st = self._static_state(x, x_info, c_info_list, guided, single)
+        st = self._static_state(x, x_info, c_info_list, guided, single, inpaint)
         if st is None:
             xs = x.clone()
             x_next, p0 = torch.empty_like(xs), torch.empty_like(xs)
             ts = torch.empty((nb,), device=dev, dtype=torch.long)
             coef = torch.empty((self.coef_width,), device=dev, dtype=torch.float32)
             bufs = dict(xs=xs, x_next=x_next, p0=p0, coef=coef, **self._extra_static(x))
+            if inpaint is not None:
+                bufs.update({k: inpaint[k] for k in ("x0", "noise", "mask")},
+                            blend=torch.empty((2,), device=dev, dtype=torch.float32))
             graph = None
             replay_first = False
         else:
@@ -221,6 +279,9 @@ class DDIMSampler(object):
             bufs = st
             replay_first = False
             xs.copy_(x)
+            if inpaint is not None:
+                for k in ("x0", "noise", "mask"):
+                    st[k].copy_(inpaint[k])
             for ci, cbuf, kv in zip(c_info_list, st["c"], st["kv"]):
                 cbuf.copy_(ci["c"])
                 ci["c"] = cbuf
@@ -277,6 +338,8 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             ts.copy_(steps_dev[i].expand(nb))       # device-side refresh, no host sync
             coef.copy_(table[index])
+            if inpaint is not None:
+                bufs["blend"].copy_(inpaint["table"][index])
             if embrow is not None:
                 embrow.copy_(emb_tab[i])
             if graph is not None and st is not None and st.get("graph_embrow", embrow is not None) != (embrow is not None):
@@ -308,9 +371,18 @@ class DDIMSampler(object):
 
     def _update_static(self, bufs, eps, guided):
         """The update at the end of a static step: reads bufs["xs"] (latent), eps and bufs["coef"], leaves the next latent in
-        bufs["xs"] and the data prediction in bufs["p0"].  Captured into the step graph with the UNet forward."""
+        bufs["xs"] and the data prediction in bufs["p0"].  Captured into the step graph with the UNet forward.  When inpainting
+        (bufs has "mask"), the latent that lands in bufs["xs"] is blended with the known region (_blend_static)."""
         ops.cfg_ddim_step_dev(bufs["xs"], eps, bufs["coef"], guided=guided, x_prev=bufs["x_next"], pred_x0=bufs["p0"])
-        bufs["xs"].copy_(bufs["x_next"])
+        if "mask" in bufs:
+            self._blend_static(bufs, bufs["x_next"])          # in place of the copy: no extra launch
+        else:
+            bufs["xs"].copy_(bufs["x_next"])
+
+    @staticmethod
+    def _blend_static(bufs, x):
+        """bufs["xs"] = mask x + (1 - mask) (blend[0] x0 + blend[1] noise) on the static inpainting buffers."""
+        ops.masked_blend(x, bufs["x0"], bufs["noise"], bufs["mask"], bufs["blend"], out=bufs["xs"])
 
     def _capture(self, body):
         try:
@@ -359,6 +431,7 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x_info, c_info, t, index, repeat_noise=False, use_original_steps=False,
                       noise_dropout=0., temperature=1.):
         """Reference-compatible single step: returns (x_prev, pred_x0)."""
+        _no_single_step_inpaint(x_info)
         assert not use_original_steps and not repeat_noise
         scale = c_info["unconditional_guidance_scale"]
         guided = scale != 1.
@@ -372,6 +445,7 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim_multicontext(self, x_info, c_info_list, t, index, repeat_noise=False, use_original_steps=False,
                                    noise_dropout=0., temperature=1.):
+        _no_single_step_inpaint(x_info)
         assert not use_original_steps and not repeat_noise
         scale = c_info_list[0]["unconditional_guidance_scale"]
         guided = scale != 1.
@@ -385,3 +459,8 @@ class DDIMSampler(object):
         xp, p0 = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
                             temperature, False, noise_dropout=noise_dropout)
         return xp.to(x.dtype), p0.to(x.dtype)
+
+
+def _no_single_step_inpaint(x_info):
+    if x_info.get("inpaint_mask") is not None:
+        raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")

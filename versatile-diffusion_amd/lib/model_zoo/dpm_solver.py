@@ -101,6 +101,8 @@ class DPMSolverSampler(DDIMSampler):
     def _update_static(self, bufs, eps, guided):
         ops.cfg_dpmpp_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], guided=guided, x_next=bufs["xs"],
                                pred_x0=bufs["p0"])
+        if "mask" in bufs:      # inpainting: the history keeps the raw data prediction, only the latent is blended
+            self._blend_static(bufs, bufs["xs"])
 
     def _step(self, *args, **kwargs):
         # the multistep update needs the history of the loop: there is no stand-alone single step (p_sample_ddim*)

@@ -10,6 +10,8 @@ app.py:309) and sliced, never re-seeded per rank, so 1-GPU and N-GPU runs produc
 import torch
 import torch.distributed as dist
 
+from ..app_ops import latent_mask
+
 
 def shard_bounds(total, world_size, rank):
     """Contiguous, balanced [lo, hi) slice of `total` samples for `rank` (earlier ranks take the remainder)."""
@@ -80,18 +82,25 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 
 
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
-                      images=None, fidelity=0., device_generator=False):
+                      images=None, fidelity=0., device_generator=False, mask=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
     the input images [n_local, 3, H, W] in [0, 1]; x0 = vae_encode(images) and only the first int(steps * (1 - fidelity))
     DDIM steps run (ddim.py:97-103).  Posterior and forward-process noise are slices of seeded full-batch draws (see
-    sample_fn), so the result does not depend on the world size."""
+    sample_fn), so the result does not depend on the world size.
+
+    images + mask: inpainting (not in the reference) -- `mask` is the pixel mask of this rank's `images` [n_local, 1, H, W]
+    or a broadcast [1, 1, H, W] (1 = regenerate, 0 = keep), turned into the latent mask by app_ops.latent_mask(mode="max").
+    x0 is encoded as above also when fidelity == 0, and then the full schedule runs from x_T."""
+    if mask is not None and images is None:
+        raise ValueError("vd_sample_sharded: mask needs images")
+
     def sample_fn(x_T, ctxs):
         for ci in ctxs:
             ci["unconditional_guidance_scale"] = guidance_scale
         lshape = [x_T.shape[0]] + list(shape[1:])
-        if images is not None and fidelity > 0.:
+        if images is not None and (fidelity > 0. or mask is not None):
             # every random number of this branch comes from a seeded FULL-batch draw sliced to this rank's samples, like
             # x_T: the forward-process noise of q_sample is the rank's slice of the x_T draw itself (the `x0_noise`
             # extension of DDIMSampler), the VAE posterior noise a second draw (seed + 1) -- never the rank's own device
@@ -101,7 +110,14 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             lo, hi = shard_bounds(shape[0], world, rank)
             post = draw_initial_latent(shape, int(seed) + 1)[lo:hi].to(x_T.device)
             x0 = net.vae_encode(images, which="image", noise=post)
-            x_info = {"type": "image", "x0": x0, "x0_forward_timesteps": int(steps * (1 - fidelity)), "x0_noise": x_T}
+            x_info = {"type": "image", "x0": x0, "x0_noise": x_T}
+            if fidelity > 0.:
+                x_info["x0_forward_timesteps"] = int(steps * (1 - fidelity))
+            else:
+                x_info["xt"] = x_T
+            if mask is not None:
+                x_info["inpaint_mask"] = latent_mask(mask.to(x_T.device), mode="max",
+                                                     factor=images.shape[-1] // shape[-1])
         else:
             x_info = {"type": "image", "xt": x_T}
         if len(ctxs) == 1:

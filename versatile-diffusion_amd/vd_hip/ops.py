@@ -953,6 +953,30 @@ def cfg_dpmpp_step_dev(x, eps, coef, x0_hist, *, guided, x_next, pred_x0=None):
     return x_next, pred_x0
 
 
+def masked_blend(x, x0, noise, mask, coef, out=None):
+    """Inpainting blend out = m x + (1 - m) (ca x0 + cn noise) with coef = device fp32 {ca, cn} (a row of
+    ddim.inpaint_blend_table).  x, x0, noise: [B, C, *spatial]; mask: [Bm, 1, *spatial] or [Bm, *spatial] with Bm = 1 or
+    B, broadcast over channels.  out may be x (in place)."""
+    _req(x, "x"); _req(x0, "x0"); _req(noise, "noise"); _req(mask, "mask"); _req(coef, "coef", torch.float32)
+    if out is None:
+        out = torch.empty_like(x)
+    _req(out, "out")
+    B, C = x.shape[0], x.shape[1]
+    n = x.numel()
+    for t, name in ((x0, "x0"), (noise, "noise"), (out, "out")):
+        if t.numel() != n:
+            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
+    hw = n // (B * C)
+    Bm = mask.shape[0]
+    if mask.numel() != Bm * hw:
+        raise VdHipError("mask has %d elements, expected %d x %d" % (mask.numel(), Bm, hw))
+    if coef.numel() < 2:
+        raise VdHipError("coef has %d elements, expected 2" % coef.numel())
+    _check(lib().vd_masked_blend_f16(_ptr(x), _ptr(x0), _ptr(noise), _ptr(mask), _ptr(out), B, C, hw, Bm, _ptr(coef),
+                                     _stream()))
+    return out
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1183,7 +1207,7 @@ def _guarded(fn):
 
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
-              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
