@@ -17,6 +17,7 @@ import torch
 from vd_hip import ops
 
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
+from .vd import kv_mark_stale, kv_refresh, kv_refreshable
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -32,11 +33,11 @@ def inpaint_blend_table(alphas_cumprod, timesteps):
 
 
 def _inpaint_args(x_info, shape):
-    """(mask, x0) of the inpainting extension keys of x_info, validated against the latent shape, or None without a
-    mask.  Runs before anything touches the device."""
+    """Whether x_info asks for inpainting, after validating its extension keys (inpaint_mask, x0) against the latent shape.
+    Runs before anything touches the device."""
     mask = x_info.get("inpaint_mask")
     if mask is None:
-        return None
+        return False
     if x_info.get("type") != "image":
         raise ValueError("inpaint_mask applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
     x0 = x_info.get("x0")
@@ -49,7 +50,7 @@ def _inpaint_args(x_info, shape):
         raise ValueError("inpaint_mask has shape %s, expected [B or 1, 1, %d, %d]" % ((tuple(mask.shape),) + shape[2:]))
     if mask.shape[0] not in (1, shape[0]):
         raise ValueError("inpaint_mask has batch %d, expected 1 or %d" % (mask.shape[0], shape[0]))
-    return mask, x0
+    return True
 
 
 class DDIMSampler(object):
@@ -101,99 +102,64 @@ class DDIMSampler(object):
         self.ddim_alphas_prev = np.asarray(alphas_prev, dtype=np.float64)
         self.ddim_sqrt_one_minus_alphas = np.sqrt(np.float32(1.) - self.ddim_alphas)
 
-    # ---- single context ---------------------------------------------------------------------------
+    # ---- entry points (single context = a list of one, `single` picks apply_model) ---------------------
     @torch.no_grad()
     def sample(self, steps, shape, x_info, c_info, eta=0., temperature=1., noise_dropout=0., verbose=True,
                log_every_t=100):
-        with self._lock:   # the schedule attributes and the kept step graphs are per-sampler state
-            self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
-            if verbose:
-                print("Data shape for DDIM sampling is {}, eta {}".format(shape, eta))
-            return self.ddim_sampling_multicontext(shape, x_info, [c_info], noise_dropout=noise_dropout,
-                                                   temperature=temperature, log_every_t=log_every_t, _single=True)
+        return self._run(shape, x_info, [c_info], noise_dropout, temperature, log_every_t, True, (steps, eta, verbose))
 
     @torch.no_grad()
     def ddim_sampling(self, shape, x_info, c_info, noise_dropout=0., temperature=1., log_every_t=100):
-        return self.ddim_sampling_multicontext(shape, x_info, [c_info], noise_dropout=noise_dropout,
-                                               temperature=temperature, log_every_t=log_every_t, _single=True)
+        return self._run(shape, x_info, [c_info], noise_dropout, temperature, log_every_t, True)
 
-    # ---- multi context ----------------------------------------------------------------------------
     @torch.no_grad()
     def sample_multicontext(self, steps, shape, x_info, c_info_list, eta=0., temperature=1., noise_dropout=0.,
                             verbose=True, log_every_t=100):
-        with self._lock:
-            self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
-            if verbose:
-                print("Data shape for DDIM sampling is {}, eta {}".format(shape, eta))
-            return self.ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout=noise_dropout,
-                                                   temperature=temperature, log_every_t=log_every_t)
+        return self._run(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, False, (steps, eta, verbose))
 
     @torch.no_grad()
     def ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout=0., temperature=1.,
                                    log_every_t=100, _single=False):
-        with self._lock:
-            return self._ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single)
+        return self._run(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single)
+
+    def _run(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, single, schedule=None):
+        """The body of the four entry points; schedule = (steps, eta, verbose) of sample*(), which set the schedule first."""
+        with self._lock:   # the schedule attributes and the kept step graphs are per-sampler state
+            if schedule is not None:
+                steps, eta, verbose = schedule
+                self.make_schedule(ddim_num_steps=steps, ddim_eta=eta, verbose=verbose)
+                if verbose:
+                    print("Data shape for DDIM sampling is {}, eta {}".format(shape, eta))
+            return self._ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, single)
 
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
-        inpaint = _inpaint_args(x_info, shape)
+        masked = _inpaint_args(x_info, shape)
         device = self.model.device
         dtype = c_info_list[0]["conditioning"].dtype
-        bs = shape[0]
-        timesteps = self.ddim_timesteps
-        blend_noise = x_info.get("x0_noise")
-        if ("xt" in x_info) and (x_info["xt"] is not None):
-            x_info["x"] = x_info["xt"].to(device=device, dtype=dtype)
-        elif ("x0" in x_info) and (x_info["x0"] is not None) and (inpaint is None or
-                                                                  x_info.get("x0_forward_timesteps") is not None):
-            x0 = x_info["x0"].to(device=device, dtype=dtype)
-            k = x_info["x0_forward_timesteps"]
-            ts = torch.full((bs,), int(timesteps[k]), device=device, dtype=torch.long)
-            timesteps = timesteps[:k]
-            # `x0_noise` (extension): inject the forward-process noise instead of drawing it, for reproducible runs
-            q_noise = x_info.get("x0_noise")
-            if inpaint is not None and q_noise is None:
-                # the draw q_sample would make (same generator use as the unmasked call); the blend reuses it
-                q_noise = blend_noise = torch.randn_like(x0)
-            x_info["x"] = self.model.q_sample(x0, ts, noise=q_noise)
-        else:
-            x_info["x"] = torch.randn(shape, device=device, dtype=dtype)
-        if inpaint is not None:
+        x_info["x"], timesteps, blend_noise = self._start_latent(shape, x_info, masked, device, dtype)
+        inpaint = None
+        if masked:
             # blended latent diffusion: one fixed noise for the whole call (x0_noise, else the start q_sample's, else x_T)
-            mask, x0 = inpaint
             f16 = dict(device=device, dtype=torch.float16)
-            inpaint = {"x0": x0.to(**f16).contiguous(), "mask": mask.to(**f16).contiguous(),
-                       "noise": (x_info["x"] if blend_noise is None else blend_noise).to(**f16).contiguous(),
+            inpaint = {"x0": x_info["x0"].to(**f16).contiguous(), "mask": x_info["inpaint_mask"].to(**f16).contiguous(),
+                       "noise": blend_noise.to(**f16).contiguous(),
                        "table": torch.from_numpy(inpaint_blend_table(self.alphas_cumprod, timesteps)).to(device)}
-
-        scale = c_info_list[0]["unconditional_guidance_scale"]
-        for ci in c_info_list:
-            assert ci["unconditional_guidance_scale"] == scale, \
-                "A different unconditional guidance scale between different context is not allowed!"
-        guided = scale != 1.
-        # the loop works on shallow copies: 'c' (the CFG batch, possibly a static buffer the captured graph reads) and
-        # 'kv_cache' never appear in the caller's dicts
-        c_info_list = [dict(ci) for ci in c_info_list]
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop
-        for ci in c_info_list:
-            if guided:
-                ci["c"] = torch.cat([ci["unconditional_conditioning"], ci["conditioning"]]).to(device)
-            else:
-                ci["c"] = ci["conditioning"].to(device)
-            ci["kv_cache"] = {}
+        c_info_list, guided, scale = self._cfg_contexts(c_info_list)
 
-        intermediates = {"pred_xt": [], "pred_x0": []}
-        time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
         x = x_info["x"].to(torch.float16).contiguous()
         eta_zero = bool(np.all(self.ddim_sigmas[:total_steps] == 0.))
         # noise_dropout > 0 (reference ddim.py:167-169 / :294-296: F.dropout on the step noise) draws a mask from the device
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
-            x, pred_x0 = self._loop_static(x, x_info, c_info_list, time_range, total_steps, guided, scale, _single,
-                                           log_every_t, intermediates, dtype, inpaint)
+            x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
+                                                 inpaint)
         else:
-            pred_x0 = None
-            for i, step in enumerate(time_range):
+            intermediates = {"pred_xt": [], "pred_x0": []}
+            for ci in c_info_list:
+                ci["kv_cache"] = {}
+            for i, step in enumerate(np.flip(timesteps)):
                 index = total_steps - i - 1
                 x, pred_x0 = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                         noise_dropout=noise_dropout)
@@ -204,6 +170,52 @@ class DDIMSampler(object):
                     intermediates["pred_x0"].append(pred_x0.to(dtype))
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
+
+    def _start_latent(self, shape, x_info, masked, device, dtype):
+        """(x, timesteps, blend_noise) of a call: the latent the loop starts from -- x_info["xt"], else x_info["x0"] diffused to
+        step x0_forward_timesteps of the schedule (which then ends there), else random x_T -- and the fixed noise an inpainting
+        call blends with.  A masked call draws from the generator exactly what the unmasked call draws."""
+        timesteps = self.ddim_timesteps
+        noise = x_info.get("x0_noise")   # extension: inject the forward-process noise instead of drawing it, for reproducible runs
+        if x_info.get("xt") is not None:
+            x = x_info["xt"].to(device=device, dtype=dtype)
+        elif x_info.get("x0") is not None and (not masked or x_info.get("x0_forward_timesteps") is not None):
+            x0 = x_info["x0"].to(device=device, dtype=dtype)
+            k = x_info["x0_forward_timesteps"]
+            ts = torch.full((shape[0],), int(timesteps[k]), device=device, dtype=torch.long)
+            timesteps = timesteps[:k]
+            if masked and noise is None:
+                # the draw q_sample would make (same generator use as the unmasked call); the blend reuses it
+                noise = torch.randn_like(x0)
+            x = self.model.q_sample(x0, ts, noise=noise)
+        else:
+            x = torch.randn(shape, device=device, dtype=dtype)
+        return x, timesteps, x if noise is None else noise
+
+    def _cfg_contexts(self, c_info_list):
+        """(copies, guided, scale): shallow copies of the contexts with 'c', the batch the UNet sees ([uncond ; cond] under
+        guidance), on the model's device.  The samplers work on the copies: 'c' (possibly a static buffer the captured graph
+        reads) and 'kv_cache' never appear in the caller's dicts."""
+        scale = c_info_list[0]["unconditional_guidance_scale"]
+        for ci in c_info_list:
+            assert ci["unconditional_guidance_scale"] == scale, \
+                "A different unconditional guidance scale between different context is not allowed!"
+        guided = scale != 1.
+        copies = [dict(ci) for ci in c_info_list]
+        for ci in copies:
+            c = torch.cat([ci["unconditional_conditioning"], ci["conditioning"]]) if guided else ci["conditioning"]
+            ci["c"] = c.to(self.model.device)
+        return copies, guided, scale
+
+    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None):
+        """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
+        so the data blocks in front of the first context block run once (extension key of this package's apply_model*)."""
+        xi = {"type": x_info["type"], "x": x, "repeat": 2 if guided else 1}
+        if emb_rows is not None:
+            xi["emb_rows"] = emb_rows
+        if single:
+            return self.model.apply_model(xi, t, c_info_list[0])
+        return self.model.apply_model_multicontext(xi, t, c_info_list)
 
     def _coef_table(self, total_steps, scale, device):
         """[S, 6] fp32 device table of {scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma, sqrt(1-a_t)}; row i is
@@ -216,12 +228,26 @@ class DDIMSampler(object):
                         self.ddim_sqrt_one_minus_alphas[:total_steps].astype(np.float64)], axis=1)
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
+    # ---- the static step loop ----------------------------------------------------------------------------
+    def _new_state(self, x, c_info_list, guided, inpaint):
+        """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
+        projections, the sampler's own buffers (_extra_static) and, when inpainting, x0 / noise / mask / blend; and the graph."""
+        nb = (2 if guided else 1) * x.shape[0]
+        st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
+              "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
+              "coef": torch.empty((self.coef_width,), device=x.device, dtype=torch.float32),
+              "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
+              "kv": [dict() for _ in c_info_list], "graph": None}
+        st.update(self._extra_static(x))
+        if inpaint is not None:
+            st.update({k: torch.empty_like(inpaint[k]) for k in ("x0", "noise", "mask")},
+                      blend=torch.empty((2,), device=x.device, dtype=torch.float32))
+        return st
+
     def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None):
-        """Buffers the captured step reads and writes, kept ACROSS sample() calls per (model weights, shapes, flow): a
-        second call with the same geometry re-uses the instantiated HIP graph instead of capturing again (capture =
-        one host-bound pass over ~400 launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  Everything
-        the graph dereferences lives here: latent buffers, step scalars, the CFG context batches and their K/V
-        projections (refreshed in place by the eager first step of every call)."""
+        """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
+        geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
+        launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
         if not self.graph_cache:
             return None
         # in-place updates / load_state_dict bump a parameter's version, .half() / .to() move its storage: the key hashes the
@@ -235,96 +261,68 @@ class DDIMSampler(object):
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
                inpaint is not None, mask_batch)
-        st = self._static.get(key)
+        st = self._static.pop(key, None)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            nb = (2 if guided else 1) * x.shape[0]
-            st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
-                  "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
-                  "coef": torch.empty((self.coef_width,), device=x.device, dtype=torch.float32),
-                  "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
-                  "kv": [dict() for _ in c_info_list], "graph": None}
-            st.update(self._extra_static(x))
-            if inpaint is not None:
-                st.update({k: torch.empty_like(inpaint[k]) for k in ("x0", "noise", "mask")},
-                          blend=torch.empty((2,), device=x.device, dtype=torch.float32))
-            self._static[key] = st
-        else:
-            self._static[key] = self._static.pop(key)          # most recently used last
+            st = self._new_state(x, c_info_list, guided, inpaint)
+        self._static[key] = st                                 # most recently used last
         return st
 
-    def _loop_static(self, x, x_info, c_info_list, time_range, total_steps, guided, scale, single, log_every_t,
-                     intermediates, dtype, inpaint=None):
-        """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
-        into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
-        sample() calls of the same geometry."""
-        dev = x.device
-        b = x.shape[0]
-        nb = 2 * b if guided else b
-        st = self._static_state(x, x_info, c_info_list, guided, single, inpaint)
-        if st is None:
-            xs = x.clone()
-            x_next, p0 = torch.empty_like(xs), torch.empty_like(xs)
-            ts = torch.empty((nb,), device=dev, dtype=torch.long)
-            coef = torch.empty((self.coef_width,), device=dev, dtype=torch.float32)
-            bufs = dict(xs=xs, x_next=x_next, p0=p0, coef=coef, **self._extra_static(x))
-            if inpaint is not None:
-                bufs.update({k: inpaint[k] for k in ("x0", "noise", "mask")},
-                            blend=torch.empty((2,), device=dev, dtype=torch.float32))
-            graph = None
-            replay_first = False
-        else:
-            xs, x_next, p0, ts, coef, graph = st["xs"], st["x_next"], st["p0"], st["ts"], st["coef"], st["graph"]
-            bufs = st
-            replay_first = False
-            xs.copy_(x)
-            if inpaint is not None:
-                for k in ("x0", "noise", "mask"):
-                    st[k].copy_(inpaint[k])
-            for ci, cbuf, kv in zip(c_info_list, st["c"], st["kv"]):
-                cbuf.copy_(ci["c"])
-                ci["c"] = cbuf
-                kv["_stale"] = set(k for k in kv if not (isinstance(k, str) and k.startswith("_")))   # K/V of the previous call's context: recomputed in place
-                ci["kv_cache"] = kv
-            if graph is not None and self.use_graph and self.replay_first and all("_modules" in kv for kv in st["kv"]):
-                # a kept graph: the context K/V projections of this call are refreshed in place right here (16 small GEMMs per
-                # context), so step 0 is replayed like every other step instead of running its ~370 launches eagerly
-                for ci, kv in zip(c_info_list, st["kv"]):
-                    cc = self.model._prep(ci["c"])
-                    for mid in list(kv["_stale"]):
-                        kv[mid].copy_(kv["_modules"][mid][0].project_context(cc))
-                    kv["_stale"].clear()
-                replay_first = True
-        table = self._coef_table(total_steps, scale, dev)
-        steps_dev = torch.from_numpy(np.ascontiguousarray(time_range).astype(np.int64)).to(dev)
-        # every sample of the batch is at the same timestep in every step, and all steps are known now: the t-only part of the
-        # forward (reference vd.py:339-349 -> openaimodel.py:2627-2633, :263) is computed here for all of them (M = steps
-        # instead of `steps` times M = batch) and the step reads row i from a static buffer
-        emb_tab = emb_rows = embrow = None
+    def _load_state(self, st, x, c_info_list, inpaint):
+        """Copy this call's latent, contexts and inpainting tensors into the state and hand its context buffers and K/V caches to
+        c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
+        st["xs"].copy_(x)
+        if inpaint is not None:
+            for k in ("x0", "noise", "mask"):
+                st[k].copy_(inpaint[k])
+        for ci, cbuf, kv in zip(c_info_list, st["c"], st["kv"]):
+            cbuf.copy_(ci["c"])
+            ci["c"] = cbuf
+            kv_mark_stale(kv)   # K/V of the previous call's context: recomputed in place
+            ci["kv_cache"] = kv
+        if not (st["graph"] is not None and self.use_graph and self.replay_first and all(kv_refreshable(kv) for kv in st["kv"])):
+            return False
+        # a kept graph: the context K/V projections of this call are refreshed in place right here (16 small GEMMs per
+        # context), so step 0 is replayed like every other step instead of running its ~370 launches eagerly
+        for ci, kv in zip(c_info_list, st["kv"]):
+            kv_refresh(kv, self.model._prep(ci["c"]))
+        return True
+
+    def _step_emb(self, st, x_info, steps_dev, single):
+        """(table [S, total], {data block index: view of st["embrow"]}) of the hoisted time embedding, or (None, None): every
+        sample of the batch is at the same timestep in every step, and all steps are known now, so the t-only part of the forward
+        (reference vd.py:339-349 -> openaimodel.py:2627-2633, :263) is computed here for all of them (M = steps instead of `steps`
+        times M = batch) and the step reads row i from the static buffer st["embrow"]."""
+        pre = None
         if self.emb_hoist and hasattr(self.model, "precompute_step_emb"):
             pre = self.model.precompute_step_emb(x_info["type"], steps_dev, multicontext=not single)
-            if pre is not None:
-                emb_tab, layout = pre
-                embrow = st.get("embrow") if st is not None else None
-                if embrow is None or embrow.numel() != emb_tab.shape[1]:
-                    assert graph is None, "the kept step graph reads another time-embedding buffer"
-                    embrow = torch.empty((emb_tab.shape[1],), device=dev, dtype=torch.float16)
-                    if st is not None:
-                        st["embrow"] = embrow
-                emb_rows = {di: embrow[o:o + c] for di, (o, c) in layout.items()}
+        if st.get("graph_embrow", pre is not None) != (pre is not None):
+            # the kept graph was captured with / without the hoisted embedding row and this call has it the other way round
+            # (precompute_step_emb started / stopped returning a table): capture again instead of replaying stale conditioning
+            st["graph"] = None
+        if pre is None:
+            return None, None
+        emb_tab, layout = pre
+        if "embrow" not in st or st["embrow"].numel() != emb_tab.shape[1]:
+            assert st["graph"] is None, "the kept step graph reads another time-embedding buffer"
+            st["embrow"] = torch.empty((emb_tab.shape[1],), device=emb_tab.device, dtype=torch.float16)
+        return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
+
+    def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None):
+        """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
+        into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
+        sample() calls of the same geometry.  Returns (final fp16 latent, intermediates)."""
+        total_steps = timesteps.shape[0]
+        st = self._static_state(x, x_info, c_info_list, guided, single, inpaint) or self._new_state(x, c_info_list, guided, inpaint)
+        replay_first = self._load_state(st, x, c_info_list, inpaint)
+        table = self._coef_table(total_steps, scale, x.device)
+        steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
+        emb_tab, emb_rows = self._step_emb(st, x_info, steps_dev, single)
 
         def body():
-            # guided: the UNet batch is [xs; xs] (ddim.py:144-149).  It is handed over as (xs, repeat=2) so the data blocks in
-            # front of the first context block run once (extension key of this package's apply_model*)
-            xi = {"type": x_info["type"], "x": xs, "repeat": 2 if guided else 1}
-            if emb_rows is not None:
-                xi["emb_rows"] = emb_rows
-            if single:
-                eps = self.model.apply_model(xi, ts, c_info_list[0])
-            else:
-                eps = self.model.apply_model_multicontext(xi, ts, c_info_list)
-            self._update_static(bufs, eps.contiguous(), guided)
+            eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows)
+            self._update_static(st, eps.contiguous(), guided)
 
         # RNG contract: the reference draws noise_like(x) = torch.randn_like(x) on every step even when sigma = 0
         # (ddim.py:167 / :294 there), so the device generator ends a sample() call advanced by one latent-sized draw per
@@ -332,38 +330,32 @@ class DDIMSampler(object):
         # (graph capture / replay bookkeeping must not leak into it), so code that keeps drawing from the default
         # generator after sample() sees the reference's stream.
         for _ in range(total_steps if self.draws_step_noise else 0):
-            torch.randn_like(xs)
-        rng_after = torch.cuda.get_rng_state(dev)
+            torch.randn_like(st["xs"])
+        rng_after = torch.cuda.get_rng_state(x.device)
+        intermediates = {"pred_xt": [], "pred_x0": []}
         for i in range(total_steps):
             index = total_steps - i - 1
-            ts.copy_(steps_dev[i].expand(nb))       # device-side refresh, no host sync
-            coef.copy_(table[index])
+            st["ts"].copy_(steps_dev[i].expand(st["ts"].shape[0]))       # device-side refresh, no host sync
+            st["coef"].copy_(table[index])
             if inpaint is not None:
-                bufs["blend"].copy_(inpaint["table"][index])
-            if embrow is not None:
-                embrow.copy_(emb_tab[i])
-            if graph is not None and st is not None and st.get("graph_embrow", embrow is not None) != (embrow is not None):
-                # the kept graph was captured with / without the hoisted embedding row and this call has it the other way round
-                # (precompute_step_emb started / stopped returning a table): capture again instead of replaying stale conditioning
-                graph = st["graph"] = None
+                st["blend"].copy_(inpaint["table"][index])
+            if emb_tab is not None:
+                st["embrow"].copy_(emb_tab[i])
             if (i == 0 and not replay_first) or not self.use_graph:
                 body()
-            elif graph is None:
-                graph = self._capture(body)
-                if graph is None:
+            else:
+                if st["graph"] is None:
+                    st["graph"] = self._capture(body)
+                    st["graph_embrow"] = emb_tab is not None
+                if st["graph"] is None:
                     body()
                 else:
-                    if st is not None:
-                        st["graph"] = graph
-                        st["graph_embrow"] = embrow is not None
-                    graph.replay()
-            else:
-                graph.replay()
+                    st["graph"].replay()
             if index % log_every_t == 0 or index == total_steps - 1:
-                intermediates["pred_xt"].append(xs.to(dtype).clone())
-                intermediates["pred_x0"].append(p0.to(dtype).clone())
-        torch.cuda.set_rng_state(rng_after, dev)
-        return xs.clone() if st is not None else xs, p0.clone() if st is not None else p0
+                intermediates["pred_xt"].append(st["xs"].to(dtype).clone())
+                intermediates["pred_x0"].append(st["p0"].to(dtype).clone())
+        torch.cuda.set_rng_state(rng_after, x.device)
+        return st["xs"].clone(), intermediates
 
     def _extra_static(self, x):
         """Further step-loop buffers (name -> tensor) of a sampler built on this loop, kept with the step graph."""
@@ -402,14 +394,8 @@ class DDIMSampler(object):
 
     def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0.):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]."""
-        b = x.shape[0]
-        nb = 2 * b if guided else b
-        t_in = torch.full((nb,), step, device=x.device, dtype=torch.long)
-        xi = {"type": x_info["type"], "x": x, "repeat": 2 if guided else 1}   # [x; x] of the reference, see _loop_static
-        if single:
-            eps = self.model.apply_model(xi, t_in, c_info_list[0])
-        else:
-            eps = self.model.apply_model_multicontext(xi, t_in, c_info_list)
+        t_in = torch.full(((2 if guided else 1) * x.shape[0],), step, device=x.device, dtype=torch.long)
+        eps = self._eps(x_info, x, t_in, c_info_list, guided, single)
         sigma = float(self.ddim_sigmas[index])
         # drawn on every step like the reference's noise_like(x) (ddim.py:167 there): same generator consumption, and for
         # eta > 0 the same noise values as a reference running in fp16 on this device
@@ -431,36 +417,19 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x_info, c_info, t, index, repeat_noise=False, use_original_steps=False,
                       noise_dropout=0., temperature=1.):
         """Reference-compatible single step: returns (x_prev, pred_x0)."""
-        _no_single_step_inpaint(x_info)
-        assert not use_original_steps and not repeat_noise
-        scale = c_info["unconditional_guidance_scale"]
-        guided = scale != 1.
-        ci = dict(c_info)
-        ci["c"] = torch.cat([c_info["unconditional_conditioning"], c_info["conditioning"]]) if guided else c_info["conditioning"]
-        x = x_info["x"]
-        xp, p0 = self._step(x.to(torch.float16).contiguous(), x_info, [ci], int(t[0]), index, guided, scale,
-                            temperature, True, noise_dropout=noise_dropout)
-        return xp.to(x.dtype), p0.to(x.dtype)
+        return self._p_sample(x_info, [c_info], t, index, repeat_noise, use_original_steps, noise_dropout, temperature, True)
 
     @torch.no_grad()
     def p_sample_ddim_multicontext(self, x_info, c_info_list, t, index, repeat_noise=False, use_original_steps=False,
                                    noise_dropout=0., temperature=1.):
-        _no_single_step_inpaint(x_info)
+        return self._p_sample(x_info, c_info_list, t, index, repeat_noise, use_original_steps, noise_dropout, temperature, False)
+
+    def _p_sample(self, x_info, c_info_list, t, index, repeat_noise, use_original_steps, noise_dropout, temperature, single):
+        if x_info.get("inpaint_mask") is not None:
+            raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")
         assert not use_original_steps and not repeat_noise
-        scale = c_info_list[0]["unconditional_guidance_scale"]
-        guided = scale != 1.
-        cis = []
-        for c_info in c_info_list:
-            assert c_info["unconditional_guidance_scale"] == scale
-            ci = dict(c_info)
-            ci["c"] = torch.cat([c_info["unconditional_conditioning"], c_info["conditioning"]]) if guided else c_info["conditioning"]
-            cis.append(ci)
+        cis, guided, scale = self._cfg_contexts(c_info_list)
         x = x_info["x"]
         xp, p0 = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
-                            temperature, False, noise_dropout=noise_dropout)
+                            temperature, single, noise_dropout=noise_dropout)
         return xp.to(x.dtype), p0.to(x.dtype)
-
-
-def _no_single_step_inpaint(x_info):
-    if x_info.get("inpaint_mask") is not None:
-        raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")

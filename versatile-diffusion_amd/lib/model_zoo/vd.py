@@ -102,6 +102,48 @@ class _BranchOrder(object):
             self.gate.record(stream)
 
 
+# ---- the context K/V cache (c_info['kv_cache']) ---------------------------------------------------------------------
+# A plain dict that callers start as {} and share between forwards on one context: id(context module) -> its projected K/V,
+# next to two entries under string keys -- the modules by the same ids (so that entries can be refreshed without a forward)
+# and the ids whose tensor still holds the projection of an earlier context.  Only the four functions below know this layout.
+_KV_MODULES, _KV_STALE = "_modules", "_stale"
+
+
+def kv_lookup(cache, module, c):
+    """K/V of context `c` [B, L, Dc] for the context block `module`: projected on first use and kept in `cache`; an entry marked
+    stale is refilled in its own storage (a captured graph reads that buffer: new context, same storage).  None without a cache."""
+    if cache is None:
+        return None
+    mid = id(module)
+    kv = cache.get(mid)
+    if kv is None:
+        kv = cache[mid] = module[0].project_context(c)
+        cache.setdefault(_KV_MODULES, {})[mid] = module
+    elif mid in cache.get(_KV_STALE, ()):
+        kv.copy_(module[0].project_context(c))
+        cache[_KV_STALE].discard(mid)
+    return kv
+
+
+def kv_mark_stale(cache):
+    """The forwards that share `cache` get a new context: every entry is recomputed in place on its next use."""
+    cache[_KV_STALE] = set(cache.get(_KV_MODULES, ()))
+
+
+def kv_refreshable(cache):
+    """Whether kv_refresh can bring `cache` up to date, i.e. a forward has filled it."""
+    return _KV_MODULES in cache
+
+
+def kv_refresh(cache, c):
+    """Recompute every stale entry in place from context `c` (prepared like the forward's: VD_v2_0._prep) without a forward."""
+    stale = cache.get(_KV_STALE, ())
+    for mid, module in cache[_KV_MODULES].items():
+        if mid in stale:
+            cache[mid].copy_(module[0].project_context(c))
+    cache[_KV_STALE] = set()
+
+
 def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
@@ -142,19 +184,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
             steps.append(("load",))
 
     def context_kv(module, spec):
-        _, c, _, cache = spec
-        kv = None
-        if cache is not None:
-            kv = cache.get(id(module))
-            stale = cache.get("_stale")
-            if kv is None:
-                kv = module[0].project_context(c)
-                cache[id(module)] = kv
-                cache.setdefault("_modules", {})[id(module)] = module   # lets the sampler refresh K/V without a forward
-            elif stale and id(module) in stale:   # buffer a captured graph reads: new context, same storage
-                kv.copy_(module[0].project_context(c))
-                stale.discard(id(module))
-        return kv
+        return kv_lookup(spec[3], module, spec[1])
 
     def run_context(h, modules, specs, rs, sl=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike."""
