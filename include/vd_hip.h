@@ -404,6 +404,33 @@ int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, 
 int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
                               int guided, const float* coef, hipStream_t stream);
 
+/* Seeded normal noise from a counter-based generator: Philox4x32-10 (Salmon et al., SC'11; Random123), multipliers
+ * 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85.  The noise of an element is a pure function of its
+ * sample's seed, so it does not depend on the batch, the batch position, the graph or the rank a sample runs in.
+ *   key     = the sample's 64-bit seed, 0 <= seed < 2^63: (low word, high word)
+ *   counter = (j, 0, draw, stream): j indexes the block of elements 4j .. 4j+3 of the sample's flattened [C, *spatial]
+ *             latent; draw is the step number in sampling order (0 for the first step run; 0 for non-step streams);
+ *             stream is 0 for x_T, 1 for forward-process (q_sample) noise, 2 for step noise
+ *   normals : output words (r0, r1) give elements 4j, 4j+1 and (r2, r3) give 4j+2, 4j+3 by Box-Muller in fp32 with
+ *             u1 = ((r_even >> 9) + 0.5) 2^-23, u2 = ((r_odd >> 9) + 0.5) 2^-23 (both exact, in (0, 1)):
+ *             z_even = sqrt(-2 ln u1) cos(2 pi u2), z_odd = sqrt(-2 ln u1) sin(2 pi u2), accurate logf / sincospif
+ * out[B, per_sample] = scale * z (fp32 when out_is_f32 != 0, else that fp32 value rounded once to fp16); any per_sample
+ * (a last partial block of four is handled).  Returns < 0 for null pointers, B or per_sample <= 0, negative draw or
+ * stream_tag, or per_sample beyond 2^34 (the block counter is one word). */
+int vd_philox_normal(const int64_t* seeds, void* out, int out_is_f32, int B, int64_t per_sample, int draw,
+                     int stream_tag, float scale, hipStream_t stream);
+
+/* vd_cfg_dpmpp_step_dev_f16 plus seeded noise: x_next = (that update) + coef[7] * z, the SDE variant of DPM-Solver++(2M)
+ * with rows of dpm_solver.dpmpp_sde_coef_table.  z is generated in place by the generator above for sample
+ * b = i / per_sample (seeds: int64[n / per_sample] in device memory) and element i % per_sample, with
+ * rng = int32[2] {draw, stream} in device memory, refreshed between graph replays like coef.  coef[7] == 0 generates
+ * nothing and gives the bits of the 2M kernel.  16-byte accesses when every pointer is 16-byte aligned and
+ * per_sample % 8 == 0, else a scalar loop with the same noise per (sample, element).  x_next may alias x.
+ * Returns < 0 for null pointers (pred_x0 may be NULL), n or per_sample <= 0, or n not a multiple of per_sample. */
+int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
+                                  int64_t per_sample, int guided, const float* coef, const int64_t* seeds,
+                                  const int* rng, hipStream_t stream);
+
 /* Masked blend of blended latent diffusion (inpainting; not in the reference), after a sampler step lands on a_prev:
  *   out = m x + (1 - m) (ca x0 + cn noise),  coef[2] = {ca, cn} = {sqrt(a_prev), sqrt(1 - a_prev)} (or {1, 0} on the
  *   last step) in device memory, fp32 math, one fp16 rounding.

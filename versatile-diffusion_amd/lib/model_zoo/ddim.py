@@ -317,6 +317,7 @@ class DDIMSampler(object):
         st = self._static_state(x, x_info, c_info_list, guided, single, inpaint) or self._new_state(x, c_info_list, guided, inpaint)
         replay_first = self._load_state(st, x, c_info_list, inpaint)
         table = self._coef_table(total_steps, scale, x.device)
+        rng_tab = self._rng_table(total_steps, x.device)
         steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
         emb_tab, emb_rows = self._step_emb(st, x_info, steps_dev, single)
 
@@ -337,6 +338,8 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             st["ts"].copy_(steps_dev[i].expand(st["ts"].shape[0]))       # device-side refresh, no host sync
             st["coef"].copy_(table[index])
+            if rng_tab is not None:
+                st["rng"].copy_(rng_tab[i])
             if inpaint is not None:
                 st["blend"].copy_(inpaint["table"][index])
             if emb_tab is not None:
@@ -356,6 +359,11 @@ class DDIMSampler(object):
                 intermediates["pred_x0"].append(st["p0"].to(dtype).clone())
         torch.cuda.set_rng_state(rng_after, x.device)
         return st["xs"].clone(), intermediates
+
+    def _rng_table(self, total_steps, device):
+        """int32 [S, 2] device table whose row i (sampling order) is copied into the sampler's static "rng" buffer
+        (_extra_static) before step i, next to the coefficient row; None: the sampler has no such buffer."""
+        return None
 
     def _extra_static(self, x):
         """Further step-loop buffers (name -> tensor) of a sampler built on this loop, kept with the step graph."""

@@ -9,6 +9,11 @@ The whole step -- UNet forward + ONE fused kernel for the CFG combine and the mu
 (ops.cfg_dpmpp_step_dev) -- is captured once into a HIP graph and replayed, exactly like DDIM: the solver's only state is
 an fp32 buffer holding the previous step's data prediction x0, and the per-step scalars are a row of the fp32[S, 8]
 table of dpmpp_coef_table, copied into a device buffer between replays.
+
+`DPMSolverSDESampler` is the stochastic variant (SDE-DPM-Solver++(2M) of the same paper; k-diffusion's dpmpp_2m_sde,
+midpoint type, in the VP parameterisation) on the same graph: its noise is generated inside the update kernel
+(ops.cfg_dpmpp_sde_step_dev) by a counter-based generator keyed by a per-sample seed (x_info["seeds"]), so the step stays
+one fused launch, nothing is drawn from torch's generator, and a sample's noise does not depend on the batch it runs in.
 """
 import numpy as np
 import torch
@@ -62,6 +67,52 @@ def dpmpp_coef_table(alphas_cumprod, timesteps, order=2, lower_order_final=True,
     return tab.astype(np.float32)
 
 
+def dpmpp_sde_coef_table(alphas_cumprod, timesteps, eta=1.0, s_noise=1.0, order=2, lower_order_final=True, scale=1.0):
+    """fp32 [S, 8] rows {scale, 1/sqrt(a_t), sqrt(1-a_t), (sg_n/sg_t) exp(-eta h), -al_n expm1(-(1+eta) h), w_cur, w_prev,
+    s_noise sg_n sqrt(-expm1(-2 eta h))} per DDIM index, computed in float64 (the layout vd_cfg_dpmpp_sde_step_dev_f16
+    reads), in the notation of dpmpp_coef_table (al / sg of a_t and a_next, h, r; the same first- and second-order rows,
+    the same ValueError for h <= 0):
+
+        x_next = (sg_n/sg_t) exp(-eta h) x + al_n (1 - exp(-(1+eta) h)) D + s_noise sg_n sqrt(1 - exp(-2 eta h)) z
+
+    with D = w_cur x0 + w_prev x0_prev as in 2M and z ~ N(0, I).  eta = 1 is SDE-DPM-Solver++(2M) (Lu et al. 2022;
+    k-diffusion's dpmpp_2m_sde, midpoint type, carried to the VP parameterisation); eta = 0 is dpmpp_coef_table bit for
+    bit (exp(-0 h) = 1 and (1 + 0) h = h are exact)."""
+    eta, s_noise = float(eta), float(s_noise)
+    if not eta >= 0.0:
+        raise ValueError("DPM-Solver++ SDE: eta must be >= 0, got %r" % (eta,))
+    tab = dpmpp_coef_table(alphas_cumprod, timesteps, order=order, lower_order_final=lower_order_final,
+                           scale=scale).astype(np.float64)
+    ts = np.asarray(timesteps)
+    _, a_t, a_next = make_ddim_sampling_parameters(alphas_cumprod, ts, 0.0, verbose=False)
+    a_t, a_next = np.asarray(a_t, np.float64), np.asarray(a_next, np.float64)
+    al_t, sg_t = np.sqrt(a_t), np.sqrt(1.0 - a_t)
+    al_n, sg_n = np.sqrt(a_next), np.sqrt(1.0 - a_next)
+    h = (np.log(al_n) - np.log(sg_n)) - (np.log(al_t) - np.log(sg_t))
+    tab[:, 3] = (sg_n / sg_t) * np.exp(-eta * h)
+    tab[:, 4] = -al_n * np.expm1(-(1.0 + eta) * h)
+    tab[:, 7] = s_noise * sg_n * np.sqrt(np.abs(np.expm1(-2.0 * eta * h)))   # expm1 <= 0; abs also turns -0.0 into 0.0
+    return tab.astype(np.float32)
+
+
+def _check_seeds(seeds, batch):
+    """x_info["seeds"] as a host int64 tensor [batch], validated: one seed per sample, each in [0, 2^63)."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int64 or seeds.dim() != 1:
+            raise ValueError("x_info['seeds'] must be an int64 tensor of shape [B], got %s %s" % (seeds.dtype, tuple(seeds.shape)))
+        vals = seeds.detach().cpu().tolist()
+    else:
+        vals = list(seeds)
+    if len(vals) != batch:
+        raise ValueError("x_info['seeds'] has %d entries, expected one per sample (%d)" % (len(vals), batch))
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("x_info['seeds'] must hold integers, got %r" % (v,))
+        if not 0 <= int(v) < 2 ** 63:
+            raise ValueError("x_info['seeds'] must lie in [0, 2^63), got %r" % (v,))
+    return torch.tensor([int(v) for v in vals], dtype=torch.int64)
+
+
 class DPMSolverSampler(DDIMSampler):
     """DPM-Solver++(2M) with classifier-free guidance; deterministic (eta = 0 only).
 
@@ -107,3 +158,98 @@ class DPMSolverSampler(DDIMSampler):
     def _step(self, *args, **kwargs):
         # the multistep update needs the history of the loop: there is no stand-alone single step (p_sample_ddim*)
         raise NotImplementedError("DPMSolverSampler runs whole sample() loops on the GPU; it has no single-step API")
+
+
+class DPMSolverSDESampler(DPMSolverSampler):
+    """SDE-DPM-Solver++(2M) with classifier-free guidance: DPMSolverSampler plus eta (1 = the SDE solver, 0 = 2M itself)
+    and `temperature` as the noise scale s_noise; noise_dropout still raises.
+
+    Noise contract: x_info["seeds"] (a sequence or int64 tensor, one seed in [0, 2^63) per sample; required when eta > 0)
+    keys a counter-based generator (ops.philox_normal; layout in include/vd_hip.h).  Step noise is generated inside the
+    update kernel (stream 2, draw = step number in sampling order), and with seeds present x_T (stream 0; when neither
+    "xt" nor "x0" is given) and the forward-process noise (stream 1; "x0" without "x0_noise") come from the same
+    generator.  The sampler then draws nothing from the device generator, and the noise a sample sees is bit-identical
+    whatever batch, batch position, graph or rank it runs in."""
+
+    def __init__(self, model, schedule="linear", order=2, lower_order_final=True, eta=1.0, **kwargs):
+        if not float(eta) >= 0.:
+            raise ValueError("DPMSolverSDESampler: eta must be >= 0, got %r" % (eta,))
+        super().__init__(model, schedule=schedule, order=order, lower_order_final=lower_order_final, **kwargs)
+        self.eta = float(eta)
+        self._eta, self._s_noise, self._seeds = self.eta, 1.0, None
+
+    @torch.no_grad()
+    def sample(self, steps, shape, x_info, c_info, eta=None, temperature=1., noise_dropout=0., verbose=True,
+               log_every_t=100):
+        return super().sample(steps, shape, x_info, c_info, eta=self.eta if eta is None else eta, temperature=temperature,
+                              noise_dropout=noise_dropout, verbose=verbose, log_every_t=log_every_t)
+
+    @torch.no_grad()
+    def sample_multicontext(self, steps, shape, x_info, c_info_list, eta=None, temperature=1., noise_dropout=0.,
+                            verbose=True, log_every_t=100):
+        return super().sample_multicontext(steps, shape, x_info, c_info_list, eta=self.eta if eta is None else eta,
+                                           temperature=temperature, noise_dropout=noise_dropout, verbose=verbose,
+                                           log_every_t=log_every_t)
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
+        if not float(ddim_eta) >= 0.:
+            raise ValueError("DPMSolverSDESampler: eta must be >= 0, got %r" % (ddim_eta,))
+        # eta belongs to the solver's own table; DDIM's sigmas stay 0, so the loop is the static one
+        self._eta = float(ddim_eta)
+        super().make_schedule(ddim_num_steps, ddim_discretize=ddim_discretize, ddim_eta=0., verbose=verbose)
+
+    def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
+        # validated before anything touches the device
+        if noise_dropout > 0.:
+            raise ValueError("DPMSolverSDESampler has no noise dropout: noise_dropout must be 0, got %r" % (noise_dropout,))
+        seeds = x_info.get("seeds")
+        if seeds is None and self._eta > 0.:
+            raise ValueError("DPMSolverSDESampler: eta = %r needs x_info['seeds'], one seed per sample" % (self._eta,))
+        self._seeds = None if seeds is None else _check_seeds(seeds, int(shape[0]))
+        self._s_noise = float(temperature)
+        return super()._ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t,
+                                                   _single)
+
+    def _start_latent(self, shape, x_info, masked, device, dtype):
+        if self._seeds is None:
+            return super()._start_latent(shape, x_info, masked, device, dtype)
+        # what the base class would draw from the device generator comes from the seeded one instead
+        xi, seeds = dict(x_info), self._seeds.to(device)
+        if xi.get("xt") is None:
+            if xi.get("x0") is not None and (not masked or xi.get("x0_forward_timesteps") is not None):
+                if xi.get("x0_noise") is None:
+                    xi["x0_noise"] = ops.philox_normal(seeds, shape, stream=1).to(dtype)
+            else:
+                xi["xt"] = ops.philox_normal(seeds, shape, stream=0).to(dtype)
+        return super()._start_latent(shape, xi, masked, device, dtype)
+
+    def _coef_table(self, total_steps, scale, device):
+        tab = dpmpp_sde_coef_table(self.alphas_cumprod, self.ddim_timesteps[:total_steps], eta=self._eta,
+                                   s_noise=self._s_noise, order=self.order, lower_order_final=self.lower_order_final,
+                                   scale=scale)
+        return torch.from_numpy(tab).to(device)
+
+    def _rng_table(self, total_steps, device):
+        # {draw, stream} per step in sampling order: the step noise is stream 2
+        draws = np.stack([np.arange(total_steps), np.full((total_steps,), 2)], axis=1).astype(np.int32)
+        return torch.from_numpy(draws).to(device)
+
+    def _extra_static(self, x):
+        return dict(super()._extra_static(x), seeds=torch.zeros((x.shape[0],), device=x.device, dtype=torch.int64),
+                    rng=torch.zeros((2,), device=x.device, dtype=torch.int32))
+
+    def _load_state(self, st, x, c_info_list, inpaint):
+        if self._seeds is None:
+            st["seeds"].zero_()          # eta = 0 without seeds: the noise coefficient is 0 and the seeds are not read
+        else:
+            st["seeds"].copy_(self._seeds)
+        return super()._load_state(st, x, c_info_list, inpaint)
+
+    def _update_static(self, bufs, eps, guided):
+        ops.cfg_dpmpp_sde_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["seeds"], bufs["rng"], guided=guided,
+                                   x_next=bufs["xs"], pred_x0=bufs["p0"])
+        if "mask" in bufs:      # inpainting: blended after the update, like the 2M sampler
+            self._blend_static(bufs, bufs["xs"])
+
+    def _step(self, *args, **kwargs):
+        raise NotImplementedError("DPMSolverSDESampler runs whole sample() loops on the GPU; it has no single-step API")

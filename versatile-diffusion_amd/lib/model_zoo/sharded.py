@@ -36,6 +36,15 @@ def draw_initial_latent(shape, seed, dtype=torch.float32, device_generator=False
     return torch.randn(tuple(shape), generator=g, dtype=torch.float32).to(dtype)
 
 
+def sample_seeds(seed, lo, hi):
+    """Per-sample noise seeds of samples [lo, hi) of a batch seeded with `seed` (DPMSolverSDESampler's x_info["seeds"]):
+    seed * 2^32 + global sample index, so a sample keeps its seed -- and with it its noise -- however the batch is split."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 31:
+        raise ValueError("sample_seeds: seed must lie in [0, 2^31), got %r" % (seed,))
+    return [seed * 2 ** 32 + i for i in range(int(lo), int(hi))]
+
+
 def _slice_ctx(c_info, lo, hi):
     out = dict(c_info)
     for k in ("conditioning", "unconditional_conditioning"):
@@ -120,6 +129,11 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                                                      factor=images.shape[-1] // shape[-1])
         else:
             x_info = {"type": "image", "xt": x_T}
+        from .dpm_solver import DPMSolverSDESampler
+        if isinstance(sampler, DPMSolverSDESampler):
+            world = dist.get_world_size(group) if dist.is_initialized() else 1
+            rank = dist.get_rank(group) if dist.is_initialized() else 0
+            x_info["seeds"] = sample_seeds(seed, *shard_bounds(shape[0], world, rank))
         if len(ctxs) == 1:
             z, _ = sampler.sample(steps=steps, shape=lshape, x_info=x_info, c_info=ctxs[0], eta=eta, verbose=False)
         else:

@@ -953,6 +953,49 @@ def cfg_dpmpp_step_dev(x, eps, coef, x0_hist, *, guided, x_next, pred_x0=None):
     return x_next, pred_x0
 
 
+def philox_normal(seeds, shape, *, draw=0, stream=0, dtype=torch.float16, scale=1.0):
+    """scale * N(0, 1) noise of shape [B, *rest] from the counter-based generator of include/vd_hip.h: row b is a pure
+    function of (seeds[b], draw, stream) and the element index, whatever the batch.  seeds: device int64 [B], each in
+    [0, 2^63) (the caller checks the range on the host); stream 0 = x_T, 1 = forward-process noise, 2 = step noise."""
+    _req(seeds, "seeds", torch.int64)
+    shape = tuple(int(s) for s in shape)
+    if dtype not in (torch.float16, torch.float32):
+        raise VdHipError("dtype must be torch.float16 or torch.float32, got %s" % (dtype,))
+    if len(shape) < 1 or any(s <= 0 for s in shape):
+        raise VdHipError("shape must be [B, ...] with positive sizes, got %s" % (shape,))
+    if seeds.dim() != 1 or seeds.numel() != shape[0]:
+        raise VdHipError("seeds has shape %s, expected [%d]" % (tuple(seeds.shape), shape[0]))
+    if int(draw) < 0 or int(stream) < 0:
+        raise VdHipError("draw and stream must be >= 0, got %r and %r" % (draw, stream))
+    out = torch.empty(shape, dtype=dtype, device=seeds.device)
+    _check(lib().vd_philox_normal(_ptr(seeds), _ptr(out), 1 if dtype == torch.float32 else 0, shape[0],
+                                  out.numel() // shape[0], int(draw), int(stream), float(scale), _stream()))
+    return out
+
+
+def cfg_dpmpp_sde_step_dev(x, eps, coef, x0_hist, seeds, rng, *, guided, x_next, pred_x0=None):
+    """cfg_dpmpp_step_dev plus coef[7] * z with z generated in the kernel (dpm_solver.dpmpp_sde_coef_table rows): seeds is a
+    device int64 [B] (x is [B, ...], one seed per sample), rng a device int32 [2] = {draw, stream} of philox_normal."""
+    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x0_hist, "x0_hist", torch.float32)
+    _req(x_next, "x_next"); _req(pred_x0, "pred_x0"); _req(seeds, "seeds", torch.int64); _req(rng, "rng", torch.int32)
+    n = x.numel()
+    if eps.numel() != (2 * n if guided else n):
+        raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
+    for t, name in ((x0_hist, "x0_hist"), (x_next, "x_next"), (pred_x0, "pred_x0")):
+        if t is not None and t.numel() != n:
+            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
+    if coef.numel() < 8:
+        raise VdHipError("coef has %d elements, expected 8" % coef.numel())
+    B = seeds.numel()
+    if B < 1 or x.dim() < 1 or x.shape[0] != B:
+        raise VdHipError("seeds has %d elements, expected one per sample of x %s" % (B, tuple(x.shape)))
+    if rng.numel() < 2:
+        raise VdHipError("rng has %d elements, expected 2" % rng.numel())
+    _check(lib().vd_cfg_dpmpp_sde_step_dev_f16(_ptr(x), _ptr(eps), _ptr(x0_hist), _ptr(x_next), _ptr(pred_x0), n, n // B,
+                                               1 if guided else 0, _ptr(coef), _ptr(seeds), _ptr(rng), _stream()))
+    return x_next, pred_x0
+
+
 def masked_blend(x, x0, noise, mask, coef, out=None):
     """Inpainting blend out = m x + (1 - m) (ca x0 + cn noise) with coef = device fp32 {ca, cn} (a row of
     ddim.inpaint_blend_table).  x, x0, noise: [B, C, *spatial]; mask: [Bm, 1, *spatial] or [Bm, *spatial] with Bm = 1 or
@@ -1207,7 +1250,7 @@ def _guarded(fn):
 
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
-              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
