@@ -232,3 +232,60 @@ def load_ref_json(name):
     import gzip
     with gzip.open(os.path.join(GOLD, name), "rt", encoding="utf-8") as f:
         return json.load(f)
+
+
+# ---- exact (tolerance-free) checks of the linear kernels: tests/exact_cases.py holds the case table --------------------
+EXACT_LIMIT = 2048        # fp16 holds every integer of magnitude <= 2048
+EXACT_ZERO_SHARE = 0.15   # a reference with more zeros than this says little about dropped terms
+
+
+def exact_operand(shape, seed):
+    """fp16 values drawn from {-1, 0, 0, +1} with equal weight on the four slots, seeded on the CPU.  Products and partial sums of
+    such operands are integers in any order, so fp32 accumulation, fp32 split-K slabs and the final fp16 rounding are all exact."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    slots = torch.tensor([-1.0, 0.0, 0.0, 1.0])
+    return slots[torch.randint(0, 4, tuple(shape), generator=g)].half()
+
+
+def exact_ints(shape, seed, lo=-8, hi=8):
+    """fp16 integers in [lo, hi] (bias, row vector, residual of the exact tests), seeded on the CPU."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g).half()
+
+
+def check_exact_reference(ref, unit=1.0, what=""):
+    """The preconditions of an exact comparison: every reference output is a multiple of `unit` (1: an integer; a power of two
+    below 1 for the fp32 outputs scaled by alpha) of magnitude <= 2048, and fewer than 15 % of them are zero."""
+    ref = torch.as_tensor(ref).double()
+    q = ref / unit
+    assert torch.equal(q, q.round()), "%s: reference is not a multiple of %g" % (what, unit)
+    peak = ref.abs().max().item()
+    assert peak <= EXACT_LIMIT, "%s: |reference| reaches %g > %d" % (what, peak, EXACT_LIMIT)
+    zeros = (ref == 0).double().mean().item()
+    assert zeros < EXACT_ZERO_SHARE, "%s: %.1f %% of the reference is zero (change the seed, not the cap)" % (what, 100 * zeros)
+    return peak, zeros
+
+
+def exact_mismatch(out, ref, names, context="", limit=6):
+    """None when `out` equals the float64 reference in every element, else a report: the number of mismatching elements, the
+    first `limit` coordinates (named by `names`, e.g. ("row", "col") or ("image", "y", "x", "channel")) with got / expected, the
+    extent of the mismatching region per axis, and `context` (the active override, variant or split)."""
+    got = torch.as_tensor(out).detach().double().cpu()
+    ref = torch.as_tensor(ref).double()
+    if tuple(got.shape) != tuple(ref.shape):
+        return "%s: shape %s, expected %s" % (context, tuple(got.shape), tuple(ref.shape))
+    if torch.equal(got, ref):
+        return None
+    bad = (got != ref) | torch.isnan(got)
+    idx = bad.nonzero()
+    lines = ["%s: %d of %d elements differ" % (context, idx.shape[0], ref.numel())]
+    lines.append("  extent: " + ", ".join("%s %d..%d" % (n, idx[:, i].min().item(), idx[:, i].max().item()) for i, n in enumerate(names)))
+    for c in idx[:limit].tolist():
+        where = ", ".join("%s=%d" % (n, v) for n, v in zip(names, c))
+        lines.append("  (%s): got %g, expected %g" % (where, got[tuple(c)].item(), ref[tuple(c)].item()))
+    return "\n".join(lines)
+
+
+def assert_exact(out, ref, names, context=""):
+    msg = exact_mismatch(out, ref, names, context)
+    assert msg is None, msg
