@@ -400,7 +400,16 @@ int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, 
  *   e = e_u + s (e_c - e_u); x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); D = w_cur x0 + w_prev x0_hist;
  *   x_next = (sigma_next/sigma_t) x + c_d D; then x0_hist = x0 (fp32[n]) and pred_x0 = x0 (fp16, may be NULL).
  * x0_hist is not read when w_prev == 0 (first-order steps).  x_next may alias x.  Lets one captured HIP graph of a
- * solver step be replayed for every step, like vd_cfg_ddim_step_dev_f16. */
+ * solver step be replayed for every step, like vd_cfg_ddim_step_dev_f16.
+ * Roundings (part of the contract; one kernel serves this entry point and vd_cfg_dpmpp_sde_step_dev_f16).  e and x0 are
+ * fma(s, e_c - e_u, e_u) and fma(-sqrt(1-a_t), e, x) / sqrt(a_t) everywhere; D and x_next depend on how an element moves:
+ *   16-byte loop (every pointer 16-byte aligned; elements [0, n/8*8)): every product-sum is one fma,
+ *       D = fma(w_prev, x0_hist, w_cur x0), x_next = fma(sigma_next/sigma_t, x, c_d D)
+ *   scalar loop (the other elements) without noise: the two products of D and of x_next are rounded before they are added
+ *   elements that get noise (the SDE entry point with coef[7] != 0), on either loop: fused as in the 16-byte loop, then
+ *       x_next = fma(coef[7], z, x_next)
+ * Each of these is an fp32 operation; x_next and pred_x0 are the fp32 results rounded to fp16 (never a sum rounded
+ * straight to fp16). */
 int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
                               int guided, const float* coef, hipStream_t stream);
 
@@ -424,8 +433,9 @@ int vd_philox_normal(const int64_t* seeds, void* out, int out_is_f32, int B, int
  * with rows of dpm_solver.dpmpp_sde_coef_table.  z is generated in place by the generator above for sample
  * b = i / per_sample (seeds: int64[n / per_sample] in device memory) and element i % per_sample, with
  * rng = int32[2] {draw, stream} in device memory, refreshed between graph replays like coef.  coef[7] == 0 generates
- * nothing and gives the bits of the 2M kernel.  16-byte accesses when every pointer is 16-byte aligned and
- * per_sample % 8 == 0, else a scalar loop with the same noise per (sample, element).  x_next may alias x.
+ * nothing and gives the bits of vd_cfg_dpmpp_step_dev_f16 (the same kernel; roundings: the rule stated there).  With noise,
+ * 16-byte accesses when every pointer is 16-byte aligned and per_sample % 8 == 0, else the scalar loop, with the same
+ * noise and the same bits per (sample, element).  x_next may alias x.
  * Returns < 0 for null pointers (pred_x0 may be NULL), n or per_sample <= 0, or n not a multiple of per_sample. */
 int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
                                   int64_t per_sample, int guided, const float* coef, const int64_t* seeds,

@@ -1,11 +1,16 @@
 """DPM-Solver++(2M) on the GPU: the fused CFG + multistep kernel (vd_cfg_dpmpp_step_dev_f16, through the C ABI) against
 an fp64 torch formula, and DPMSolverSampler against DDIMSampler (order 1) and against the fp32 CPU oracle driven by the
-same coefficient table (order 2); graph replay and kept graphs, the RNG contract and the sharding helper."""
+same coefficient table (order 2); the bits of every fused sampler step against tests/golden/sampler_step_bits.json; graph
+replay and kept graphs, the RNG contract and the sharding helper."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from vdtest_util import full_vd_cfg, load_gold, meta, rel_l2, synth_into, tiny_vd_cfg
+from vdtest_util import GOLD, full_vd_cfg, load_gold, meta, rel_l2, synth_into, tiny_vd_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +116,31 @@ def test_kernel_vs_fp64_formula(dev, n, offset, guided, alias):
     gen = torch.Generator().manual_seed(n + 7 * offset + 3 * guided + alias)
     r = _kernel_case(dev, n, guided, offset, alias, gen)
     assert r[6] != 0          # the second call really was a second-order step
+
+
+@pytest.mark.parametrize("family", ["solver", "ddim"])
+def test_sampler_step_bits_match_the_fixture(dev, family):
+    """Every output of the fused CFG + sampler updates (2M, SDE at eta = 1 and eta = 0, DDIM with host and device scalars),
+    byte for byte, against the digests tools/gen_sampler_step_bits.py recorded: the fixture, not the compiler, says what the
+    bits of a step are (both loops of the solver kernel included: the fixture's largest case tells their roundings apart)."""
+    from vd_hip import ops
+    spec = importlib.util.spec_from_file_location(
+        "gen_sampler_step_bits", os.path.join(os.path.dirname(GOLD), os.pardir, "tools", "gen_sampler_step_bits.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(GOLD, "sampler_step_bits.json")) as f:
+        fix = json.load(f)
+    assert fix["B"] == tool.B and fix["big_per"] >= 16384
+    big = [c["2m"] for c in fix["solver"] if c["per"] == fix["big_per"] and c["guided"]]
+    assert len(big) == 2 and all(a["x_next"] != b["x_next"] for a, b in zip(*big))      # the fixture can tell the loops apart
+    for want in fix[family]:
+        if family == "solver":
+            got = tool.solver_case(ops, dev, want["per"], want["offset"], want["guided"])
+        else:
+            got = tool.ddim_case(ops, dev, want["offset"], want["guided"], want["noise"])
+        assert got["inputs"] == want["inputs"], "inputs changed (torch draws differently?): %r" % (
+            {k: v for k, v in want.items() if not isinstance(v, (list, dict))},)
+        assert got == want
 
 
 # ---- 2. order 1 == DDIM (eta = 0) ---------------------------------------------------------------------------------------

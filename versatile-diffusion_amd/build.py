@@ -31,8 +31,10 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "ff_fused.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
                "ff_chain.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
                "gemm_row320.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
-               # the SDE solver update: packed-fp32 forms of the unrolled 8-element update duplicate every step scalar into a
-               # scalar register pair per use; with the inlined logf / sincospif of the generator that spills 33 scalar registers
+               # the DPM-Solver++ update (2M and SDE instances of one kernel): packed-fp32 forms of the unrolled 8-element
+               # update duplicate every step scalar into a scalar register pair per use; with the inlined logf / sincospif of
+               # the generator that spills 33 scalar registers.  The update's roundings are written out in the source, so
+               # this flag does not decide its bits.
                "noise.hip": ["-fno-slp-vectorize"]}
 
 

@@ -1,6 +1,7 @@
 // HBM-bound helper kernels of the sampling path (gfx950): timestep embedding, fused CFG + DDIM
-// update, q_sample, layout changes at the NCHW API boundary, small-Cin im2col, VAE posterior
-// sampling, and the CLIP embedding / pooled-norm helpers.  All math in fp32, storage fp16.
+// update (the DPM-Solver++ update is in noise.hip), inpainting blend, q_sample, layout changes at
+// the NCHW API boundary, small-Cin im2col, VAE posterior sampling, and the CLIP embedding /
+// pooled-norm helpers.  All math in fp32, storage fp16.
 #include "vd_common.h"
 #include "../../include/vd_hip.h"
 #include <stdarg.h>
@@ -32,13 +33,6 @@ extern "C" int vd_abi_version(void) { return VD_HIP_ABI_VERSION; }
 
 namespace {
 
-inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
-    size_t g = (n + per_block - 1) / per_block;
-    if (g > (size_t)cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // lib/model_zoo/diffusion_utils.py:131-151 -- freqs = exp(-ln(max_period) * i / half), [cos | sin]
 __global__ void timestep_embedding_kernel(const int64_t* t, f16* out, int B, int dim, float log_max_period) {
     const int half = dim / 2;
@@ -52,30 +46,18 @@ __global__ void timestep_embedding_kernel(const int64_t* t, f16* out, int B, int
     }
 }
 
-// lib/model_zoo/ddim.py:144-170
-__global__ void cfg_ddim_kernel(const f16* x, const f16* eps, const f16* noise, f16* x_prev, f16* pred_x0, size_t n,
-                                int guided, float s, float rsqrt_at, float sqrt_aprev, float dir_coef, float sigma,
-                                float sqrt_1mat) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float e = (float)eps[i];
-        if (guided) {
-            const float ec = (float)eps[n + i];
-            e = e + s * (ec - e);
-        }
-        const float xv = (float)x[i];
-        const float p0 = (xv - sqrt_1mat * e) * rsqrt_at;
-        float xp = sqrt_aprev * p0 + dir_coef * e;
-        if (noise != nullptr) xp += sigma * (float)noise[i];
-        x_prev[i] = (f16)xp;
-        if (pred_x0 != nullptr) pred_x0[i] = (f16)p0;
-    }
-}
+// lib/model_zoo/ddim.py:144-170.  The six step scalars {guidance scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1 - a_prev - sigma^2),
+// sigma, sqrt(1 - a_t)} come either by value (DdimCoef, filled by the host) or from device memory (const float*), so that ONE
+// captured HIP graph serves all DDIM steps.
+struct DdimCoef { float v[6]; };
+__device__ __forceinline__ float ddim_coef(const DdimCoef& c, int k) { return c.v[k]; }
+__device__ __forceinline__ float ddim_coef(const float* c, int k) { return c[k]; }
 
-// same update with the six step scalars read from device memory, so ONE captured HIP graph serves all DDIM steps
-// coef = {guidance scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1 - a_prev - sigma^2), sigma, sqrt(1 - a_t)}
-__global__ void cfg_ddim_dev_kernel(const f16* x, const f16* eps, const f16* noise, f16* x_prev, f16* pred_x0, size_t n,
-                                    int guided, const float* coef) {
-    const float s = coef[0], rsqrt_at = coef[1], sqrt_aprev = coef[2], dir_coef = coef[3], sigma = coef[4], sqrt_1mat = coef[5];
+template <typename Coef>
+__global__ void cfg_ddim_kernel(const f16* x, const f16* eps, const f16* noise, f16* x_prev, f16* pred_x0, size_t n,
+                                int guided, Coef coef) {
+    const float s = ddim_coef(coef, 0), rsqrt_at = ddim_coef(coef, 1), sqrt_aprev = ddim_coef(coef, 2),
+                dir_coef = ddim_coef(coef, 3), sigma = ddim_coef(coef, 4), sqrt_1mat = ddim_coef(coef, 5);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float e = (float)eps[i];
         if (guided) {
@@ -87,66 +69,6 @@ __global__ void cfg_ddim_dev_kernel(const f16* x, const f16* eps, const f16* noi
         if (noise != nullptr) xp += sigma * (float)noise[i];
         x_prev[i] = (f16)xp;
         if (pred_x0 != nullptr) pred_x0[i] = (f16)p0;
-    }
-}
-
-// CFG combine + DPM-Solver++(2M) multistep update, step scalars in device memory (one captured graph serves all steps):
-// coef = {guidance scale, 1/sqrt(a_t), sqrt(1 - a_t), sigma_next / sigma_t, c_d, w_cur, w_prev, 0}
-//   x0 = (x - sqrt(1-a_t) e) / sqrt(a_t);  D = w_cur x0 + w_prev x0_hist;  x_next = (sigma_next / sigma_t) x + c_d D
-// then x0_hist = x0 (fp32).  w_prev == 0 (first-order rows) never reads x0_hist: it is uninitialised on the first step of a
-// call.  x_next may alias x (each element is read and written by the same lane).  vec != 0: every pointer is 16-byte
-// aligned (the host checks), so elements [0, n/8*8) move as 8 x fp16 / 2 x float4 per lane; the rest take the scalar loop.
-__device__ __forceinline__ float dpmpp_elem(float x, float eu, float ec, float h, int guided, bool second, float s,
-                                            float rsqrt_at, float sqrt_1mat, float ratio, float c_d, float w_cur,
-                                            float w_prev, float& x0) {
-    const float e = guided ? eu + s * (ec - eu) : eu;
-    x0 = (x - sqrt_1mat * e) * rsqrt_at;
-    float d = w_cur * x0;
-    if (second) d += w_prev * h;
-    return ratio * x + c_d * d;
-}
-
-__global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_hist, f16* x_next, f16* pred_x0, size_t n,
-                                     int guided, int vec, const float* coef) {
-    const float s = coef[0], rsqrt_at = coef[1], sqrt_1mat = coef[2], ratio = coef[3], c_d = coef[4], w_cur = coef[5],
-                w_prev = coef[6];
-    const bool second = w_prev != 0.f;          // uniform over the grid
-    const f16* eps_c = eps + n;
-    const size_t nv = vec ? n / 8 : 0;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
-        U4H8 xv, eu, ec, xo, po;
-        xv.u = reinterpret_cast<const uint4*>(x)[i];
-        eu.u = reinterpret_cast<const uint4*>(eps)[i];
-        if (guided) ec.u = reinterpret_cast<const uint4*>(eps_c)[i];
-        float h[8], x0[8];
-        float4* hp = reinterpret_cast<float4*>(x0_hist) + 2 * i;
-        if (second) {
-            const float4 h0 = hp[0], h1 = hp[1];
-            h[0] = h0.x; h[1] = h0.y; h[2] = h0.z; h[3] = h0.w; h[4] = h1.x; h[5] = h1.y; h[6] = h1.z; h[7] = h1.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) h[j] = 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xn = dpmpp_elem((float)xv.e[j], (float)eu.e[j], guided ? (float)ec.e[j] : 0.f, h[j], guided, second,
-                                        s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0[j]);
-            xo.e[j] = (f16)xn;
-            po.e[j] = (f16)x0[j];
-        }
-        reinterpret_cast<uint4*>(x_next)[i] = xo.u;
-        hp[0] = make_float4(x0[0], x0[1], x0[2], x0[3]);
-        hp[1] = make_float4(x0[4], x0[5], x0[6], x0[7]);
-        if (pred_x0 != nullptr) reinterpret_cast<uint4*>(pred_x0)[i] = po.u;
-    }
-    for (size_t i = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float x0;
-        const float xn = dpmpp_elem((float)x[i], (float)eps[i], guided ? (float)eps_c[i] : 0.f, second ? x0_hist[i] : 0.f,
-                                    guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
-        x_next[i] = (f16)xn;
-        x0_hist[i] = x0;
-        if (pred_x0 != nullptr) pred_x0[i] = (f16)x0;
     }
 }
 
@@ -452,39 +374,26 @@ extern "C" int vd_cfg_ddim_step_f16(const void* x, const void* eps, const void* 
     VD_REQUIRE(a_t > 0.f && a_prev >= 0.f, "vd_cfg_ddim_step_f16: alphas must be positive");
     float dir2 = 1.f - a_prev - sigma * sigma;
     if (dir2 < 0.f) dir2 = 0.f;
-    hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
-                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided,
-                       guidance_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(dir2), sigma, sqrt_one_minus_at);
+    const DdimCoef coef = {{guidance_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(dir2), sigma, sqrt_one_minus_at}};
+    hipLaunchKernelGGL(cfg_ddim_kernel<DdimCoef>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
+                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef);
     return vd_check_launch("vd_cfg_ddim_step_f16");
 }
 
 extern "C" int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0,
                                         int64_t n, int guided, const float* coef, hipStream_t stream) {
     VD_REQUIRE(x && eps && x_prev && coef && n > 0, "vd_cfg_ddim_step_dev_f16: bad arguments");
-    hipLaunchKernelGGL(cfg_ddim_dev_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
+    hipLaunchKernelGGL(cfg_ddim_kernel<const float*>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
                        (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef);
     return vd_check_launch("vd_cfg_ddim_step_dev_f16");
-}
-
-extern "C" int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
-                                         int64_t n, int guided, const float* coef, hipStream_t stream) {
-    VD_REQUIRE(x && eps && x0_hist && x_next && coef && n > 0, "vd_cfg_dpmpp_step_dev_f16: bad arguments");
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    // torch slices can start anywhere: the 16-byte path only when every stream (both eps halves included) is aligned
-    const int vec = a16(x) && a16(eps) && (!guided || a16((const f16*)eps + n)) && a16(x0_hist) && a16(x_next) &&
-                    (pred_x0 == nullptr || a16(pred_x0));
-    const size_t work = vec ? (size_t)(n + 7) / 8 : (size_t)n;
-    hipLaunchKernelGGL(cfg_dpmpp_dev_kernel, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
-                       x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, vec, coef);
-    return vd_check_launch("vd_cfg_dpmpp_step_dev_f16");
 }
 
 extern "C" int vd_masked_blend_f16(const void* x, const void* x0, const void* noise, const void* mask, void* out, int B,
                                    int C, int64_t HW, int Bm, const float* coef, hipStream_t stream) {
     VD_REQUIRE(x && x0 && noise && mask && out && coef && B > 0 && C > 0 && HW > 0, "vd_masked_blend_f16: bad arguments");
     VD_REQUIRE(Bm == 1 || Bm == B, "vd_masked_blend_f16: mask batch %d must be 1 or B = %d", Bm, B);
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const int vec = HW % 8 == 0 && a16(x) && a16(x0) && a16(noise) && a16(mask) && a16(out);
+    const int vec = HW % 8 == 0 && vd_aligned16(x) && vd_aligned16(x0) && vd_aligned16(noise) && vd_aligned16(mask) &&
+                    vd_aligned16(out);
     const size_t n = (size_t)B * C * HW;
     const size_t work = vec ? n / 8 : n;
     hipLaunchKernelGGL(masked_blend_kernel, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x, (const f16*)x0,

@@ -110,13 +110,15 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
     gw_static_for<0, 4>([&](auto st) { load_w(std::integral_constant<int, 0>{}, st, c_begin); });
     gw_static_for<0, 4>([&](auto st) { load_w(std::integral_constant<int, 1>{}, st, c_begin + 1); });
 
-    auto chunk = [&](auto pt, int lc) {
-        constexpr int par = decltype(pt)::value;
+    auto chunk = [&](auto lt) {
+        constexpr int lc = decltype(lt)::value, par = lc & 1;
+        const std::integral_constant<int, par> pt;
         const int c = c_begin + lc;
         // this chunk's activation tile (requested during the previous chunk, in front of the 8 weight loads of chunk c + 1) and
         // its weights (requested two chunks ago) have landed for this wave ... for every wave; every wave has left chunk c - 1,
-        // whose buffer the DMA below refills
-        wait_vm<8>();
+        // whose buffer the DMA below refills.  The last chunk a block can have has no weight loads behind its tile (chunk
+        // GW_MAXC + 1 does not exist, see below), so its tile is the newest request in flight: a count of 8 would not cover it
+        wait_vm<(lc + 1 < GW_MAXC ? 8 : 0)>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (lc + 1 < ncl) issue_a(c + 1, par ^ 1);
@@ -136,7 +138,9 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[par][ks][j].h, bf[i], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            load_w(pt, kt, c + 2);   // always issued (clamped): every chunk adds exactly 8 weight loads behind its DMA pieces
+            // issued whether or not chunk c + 2 is this block's (clamped): every chunk adds exactly 8 weight loads behind its
+            // DMA pieces -- except where no block has a chunk lc + 2, which the wait of chunk lc + 1 above accounts for
+            if constexpr (lc + 2 < GW_MAXC) load_w(pt, kt, c + 2);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
     // 36-k-step chunk; here it would be every second 4-k-step chunk).
     gw_static_for<0, GW_MAXC>([&](auto lt) {
         constexpr int lc = decltype(lt)::value;
-        if (lc < ncl) chunk(std::integral_constant<int, lc & 1>{}, lc);
+        if (lc < ncl) chunk(lt);
     });
 
     // ---- fp32 slab of this split for the reduce kernel, straight from registers (4 consecutive floats per lane and group)

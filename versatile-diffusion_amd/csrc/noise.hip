@@ -1,19 +1,14 @@
 // Seeded noise made where it is used (gfx950): a counter-based Philox4x32-10 generator with a Box-Muller normal map, the
-// kernel that fills a tensor with it, and the SDE variant of the fused CFG + DPM-Solver++(2M) update, which adds its noise
-// term in place.  Contract (key, counter, normal map): include/vd_hip.h.
+// kernel that fills a tensor with it, and the fused CFG + DPM-Solver++(2M) update: one kernel, instantiated without noise (the
+// 2M sampler) and with its noise term added in place (the SDE variant).  Contract (key, counter, normal map, the update's
+// roundings): include/vd_hip.h.
 // Built with -fno-slp-vectorize (build.py): the packed-fp32 forms of the unrolled 8-element update want every step scalar
-// duplicated into a scalar register pair per use, which on top of the inlined logf / sincospif spills scalar registers.
+// duplicated into a scalar register pair per use, which on top of the inlined logf / sincospif spills scalar registers.  The
+// update's roundings are written out (dpmpp_elem_exact), so the flag decides registers, not bits.
 #include "vd_common.h"
 #include "../../include/vd_hip.h"
 
 namespace {
-
-inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
-    size_t g = (n + per_block - 1) / per_block;
-    if (g > (size_t)cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
 
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123) in plain integer
 // arithmetic: a counter-based generator, so the noise of (sample, draw, element) is a pure function of the sample's seed and
@@ -87,14 +82,11 @@ __global__ void philox_normal_kernel(const int64_t* seeds, T* out, int B, size_t
     }
 }
 
-// The per-element CFG combine + DPM-Solver++(2M) update of cfg_dpmpp_dev_kernel (elementwise.hip: dpmpp_elem), with its
-// roundings written out instead of left to -ffp-contract=fast, so that they do not depend on the loop an element is handled by:
+// The per-element CFG combine + DPM-Solver++(2M) update, with its roundings written out instead of left to -ffp-contract=fast:
 //   e = eu + s (ec - eu);  x0 = (x - sqrt_1mat e) rsqrt_at;  D = w_cur x0 + w_prev h;  x_next = ratio x + c_d D
-// SPLIT = false: every product-sum is one fma -- what the 2M kernel's 16-byte loop is compiled to, and the form of every
-// element that gets noise.  SPLIT = true: the two products of D and of x_next are rounded before they are added -- what the
-// 2M kernel's scalar loop is compiled to, its products paired into packed multiplies; written here as the same packed
-// multiplies (a scalar product feeding an add would be fused whatever the source says).  Used only by the scalar loop at
-// coef[7] == 0, where this kernel has to give the 2M kernel's bits.
+// SPLIT = false: every product-sum is one fma.  SPLIT = true: the two products of D and of x_next are rounded before they are
+// added; written as packed multiplies (a scalar product feeding an add would be fused whatever the source says).  e and x0 are
+// fused in both forms.  Which element takes which form: the rule above cfg_dpmpp_dev_kernel.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <bool SPLIT>
@@ -114,25 +106,52 @@ __device__ __forceinline__ float dpmpp_elem_exact(float x, float eu, float ec, f
     return fmaf(ratio, x, c_d * d);
 }
 
-// The 2M update plus coef[7] z, the SDE variant of DPM-Solver++(2M) (dpm_solver.dpmpp_sde_coef_table): z is made in place from
-// seeds[i / per_sample] and the element index i % per_sample, with rng = {draw, stream} in device memory (refreshed between
-// graph replays like coef).  coef[7] == 0 (uniform over the grid) generates nothing and walks the elements exactly as the 2M
-// kernel does, so it gives that kernel's bits.  VEC: every pointer is 16-byte aligned (the host checks); then elements
-// [0, n/8*8) move as 8 x fp16 per lane, as in the 2M kernel -- with noise only if per_sample % 8 == 0, so that the 8 elements of
-// a lane lie in one sample and take two Philox blocks.  Every other element goes through the scalar loop, which picks its
-// normal out of its block by the same functions: the same bits for the same (sample, element) on either path.
-template <bool VEC>
-__global__ void cfg_dpmpp_sde_dev_kernel(const f16* x, const f16* eps, float* x0_hist, f16* x_next, f16* pred_x0, size_t n,
-                                         size_t per_sample, int guided, const float* coef, const int64_t* seeds,
-                                         const int* rng) {
+// fp32 -> fp16 as a rounding of its own.  Left to the compiler, a conversion that follows an fma whose operand was widened from
+// fp16 is folded into it (v_fma_mixlo_f16 / v_fma_mixhi_f16), and that instruction rounds the exact sum once to fp16: other
+// bits than the fp32 fma followed by the conversion, in about one output per 10^4.  The empty asm keeps the fp32 value apart.
+__device__ __forceinline__ f16 round_f16(float v) {
+    asm("" : "+v"(v));
+    return (f16)v;
+}
+
+// where the noise of a step comes from: seeds[i / per_sample] and rng = {draw, stream} in device memory (refreshed between
+// graph replays like coef).  Empty without noise, so those instances take no seeds and hold no generator code.
+template <bool NOISE> struct StepNoise {};
+template <> struct StepNoise<true> { const int64_t* seeds; const int* rng; size_t per_sample; };
+
+// CFG combine + DPM-Solver++(2M) multistep update, step scalars in device memory (one captured graph serves all steps):
+// coef = {guidance scale, 1/sqrt(a_t), sqrt(1 - a_t), sigma_next / sigma_t, c_d, w_cur, w_prev, c_z}, then x0_hist = x0 (fp32).
+// w_prev == 0 (first-order rows) never reads x0_hist: it is uninitialised on the first step of a call.  x_next may alias x
+// (each element is read and written by the same lane).
+// NOISE = false is the 2M update: coef[7] is not read.  NOISE = true adds coef[7] z, the SDE variant of DPM-Solver++(2M)
+// (dpm_solver.dpmpp_sde_coef_table), z made in place from the sample's seed and the element index i % per_sample; coef[7] == 0
+// (uniform over the grid) generates nothing and walks the elements exactly as NOISE = false does.
+// VEC: every pointer is 16-byte aligned (the host checks); then elements [0, n/8*8) move as 8 x fp16 / 2 x float4 per lane --
+// with noise only if per_sample % 8 == 0, so that the 8 elements of a lane lie in one sample and take two Philox blocks.  Every
+// other element goes through the scalar loop, which picks its normal out of its block by the same functions: the same bits
+// for the same (sample, element) on either path.
+// Roundings (the ABI's rule, include/vd_hip.h), in terms of dpmpp_elem_exact:
+//   elements moved by the 16-byte loop             every product-sum is one fma (SPLIT = false)
+//   elements of the scalar loop without noise      the two products of D and of x_next are rounded, then added (SPLIT = true)
+//   elements that get noise, on either loop        fused (SPLIT = false), then x_next = fma(c_z, z, x_next)
+// and x_next, pred_x0 are those fp32 values rounded to fp16 (round_f16), never a sum rounded straight to fp16.
+template <bool VEC, bool NOISE>
+__global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_hist, f16* x_next, f16* pred_x0, size_t n,
+                                     int guided, const float* coef, StepNoise<NOISE> src) {
     const float s = coef[0], rsqrt_at = coef[1], sqrt_1mat = coef[2], ratio = coef[3], c_d = coef[4], w_cur = coef[5],
-                w_prev = coef[6], c_z = coef[7];
+                w_prev = coef[6];
     const bool second = w_prev != 0.f;          // uniform over the grid
-    const bool noisy = c_z != 0.f;              // uniform over the grid
-    const uint32_t draw = (uint32_t)rng[0], stream = (uint32_t)rng[1];
+    float c_z = 0.f;
+    uint32_t draw = 0, stream = 0;
+    bool lanes8 = VEC;
+    if constexpr (NOISE) {
+        c_z = coef[7];
+        draw = (uint32_t)src.rng[0], stream = (uint32_t)src.rng[1];
+        // with noise the lane's group index is divided in 32 bits: groups of 8 per sample, and n / 8 must fit one word
+        lanes8 = VEC && (c_z == 0.f || (src.per_sample % 8 == 0 && n / 8 <= 0xffffffffull));
+    }
+    const bool noisy = c_z != 0.f;              // uniform over the grid; false at compile time without NOISE
     const f16* eps_c = eps + n;
-    // with noise the lane's group index is divided in 32 bits: groups of 8 per sample, and n / 8 must fit one word
-    const bool lanes8 = VEC && (!noisy || (per_sample % 8 == 0 && n / 8 <= 0xffffffffull));
     const size_t nv = lanes8 ? n / 8 : 0;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
@@ -149,19 +168,21 @@ __global__ void cfg_dpmpp_sde_dev_kernel(const f16* x, const f16* eps, float* x0
 #pragma unroll
             for (int j = 0; j < 8; ++j) h[j] = 0.f;
         }
-        if (noisy) {
-            const uint32_t g = (uint32_t)(per_sample >> 3), b = (uint32_t)i / g, j = 2u * ((uint32_t)i - b * g);
-            const PhiloxKey key = philox_key(seeds, b);
-            philox_normal4(key, j, draw, stream, z);
-            philox_normal4(key, j + 1u, draw, stream, z + 4);
+        if constexpr (NOISE) {
+            if (noisy) {
+                const uint32_t g = (uint32_t)(src.per_sample >> 3), b = (uint32_t)i / g, j = 2u * ((uint32_t)i - b * g);
+                const PhiloxKey key = philox_key(src.seeds, b);
+                philox_normal4(key, j, draw, stream, z);
+                philox_normal4(key, j + 1u, draw, stream, z + 4);
+            }
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float xn = dpmpp_elem_exact<false>((float)xv.e[j], (float)eu.e[j], guided ? (float)ec.e[j] : 0.f, h[j], guided,
                                                second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0[j]);
             if (noisy) xn = fmaf(c_z, z[j], xn);
-            xo.e[j] = (f16)xn;
-            po.e[j] = (f16)x0[j];
+            xo.e[j] = round_f16(xn);
+            po.e[j] = round_f16(x0[j]);
         }
         reinterpret_cast<uint4*>(x_next)[i] = xo.u;
         hp[0] = make_float4(x0[0], x0[1], x0[2], x0[3]);
@@ -171,17 +192,34 @@ __global__ void cfg_dpmpp_sde_dev_kernel(const f16* x, const f16* eps, float* x0
     for (size_t i = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xf = (float)x[i], euf = (float)eps[i], ecf = guided ? (float)eps_c[i] : 0.f, hf = second ? x0_hist[i] : 0.f;
         float x0, xn;
-        if (noisy) {
-            const size_t b = i / per_sample;
-            xn = dpmpp_elem_exact<false>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
-            xn = fmaf(c_z, philox_normal1(philox_key(seeds, b), i - b * per_sample, draw, stream), xn);
-        } else {
+        if (!noisy) {
             xn = dpmpp_elem_exact<true>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
+        } else if constexpr (NOISE) {
+            const size_t b = i / src.per_sample;
+            xn = dpmpp_elem_exact<false>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
+            xn = fmaf(c_z, philox_normal1(philox_key(src.seeds, b), i - b * src.per_sample, draw, stream), xn);
         }
-        x_next[i] = (f16)xn;
+        x_next[i] = round_f16(xn);
         x0_hist[i] = x0;
-        if (pred_x0 != nullptr) pred_x0[i] = (f16)x0;
+        if (pred_x0 != nullptr) pred_x0[i] = round_f16(x0);
     }
+}
+
+// Both entry points' launch.  The alignment rule: 16-byte lanes only when every stream (both eps halves included) is aligned
+// (torch slices can start anywhere).  lanes8: a lane of the aligned kernel takes 8 elements (sizes the grid; whether a noisy
+// step can use the lanes, per_sample % 8 == 0, is the kernel's call).
+template <bool NOISE>
+void launch_dpmpp(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n, int guided,
+                  const float* coef, bool lanes8, StepNoise<NOISE> src, hipStream_t stream) {
+    const bool vec = vd_aligned16(x) && vd_aligned16(eps) && (!guided || vd_aligned16((const f16*)eps + n)) &&
+                     vd_aligned16(x0_hist) && vd_aligned16(x_next) && (pred_x0 == nullptr || vd_aligned16(pred_x0));
+    const int grid = grid_for(vec && lanes8 ? (size_t)(n + 7) / 8 : (size_t)n);
+    if (vec)
+        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<true, NOISE>), dim3(grid), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
+                           x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src);
+    else
+        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<false, NOISE>), dim3(grid), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
+                           x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src);
 }
 
 }  // namespace
@@ -201,6 +239,13 @@ extern "C" int vd_philox_normal(const int64_t* seeds, void* out, int out_is_f32,
     return vd_check_launch("vd_philox_normal");
 }
 
+extern "C" int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
+                                         int64_t n, int guided, const float* coef, hipStream_t stream) {
+    VD_REQUIRE(x && eps && x0_hist && x_next && coef && n > 0, "vd_cfg_dpmpp_step_dev_f16: bad arguments");
+    launch_dpmpp<false>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, true, StepNoise<false>{}, stream);
+    return vd_check_launch("vd_cfg_dpmpp_step_dev_f16");
+}
+
 extern "C" int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
                                              int64_t n, int64_t per_sample, int guided, const float* coef,
                                              const int64_t* seeds, const int* rng, hipStream_t stream) {
@@ -210,18 +255,7 @@ extern "C" int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, flo
                (long long)n, (long long)per_sample);
     VD_REQUIRE((per_sample + 3) / 4 <= (int64_t)1 << 32,
                "vd_cfg_dpmpp_sde_step_dev_f16: per_sample %lld exceeds the 32-bit block counter", (long long)per_sample);
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    // the 2M kernel's alignment rule; whether a noisy step can use the 16-byte lanes (per_sample % 8 == 0) is the kernel's call
-    const int vec = a16(x) && a16(eps) && (!guided || a16((const f16*)eps + n)) && a16(x0_hist) &&
-                    a16(x_next) && (pred_x0 == nullptr || a16(pred_x0));
-    const size_t work = vec && per_sample % 8 == 0 ? (size_t)(n + 7) / 8 : (size_t)n;
-    if (vec)
-        hipLaunchKernelGGL(cfg_dpmpp_sde_dev_kernel<true>, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x,
-                           (const f16*)eps, x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, (size_t)per_sample, guided, coef,
-                           seeds, rng);
-    else
-        hipLaunchKernelGGL(cfg_dpmpp_sde_dev_kernel<false>, dim3(grid_for(work)), dim3(256), 0, stream, (const f16*)x,
-                           (const f16*)eps, x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, (size_t)per_sample, guided, coef,
-                           seeds, rng);
+    launch_dpmpp<true>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, per_sample % 8 == 0,
+                       StepNoise<true>{seeds, rng, (size_t)per_sample}, stream);
     return vd_check_launch("vd_cfg_dpmpp_sde_step_dev_f16");
 }

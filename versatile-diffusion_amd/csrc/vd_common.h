@@ -27,6 +27,16 @@ int vd_check_launch(const char* what);
         }                                     \
     } while (0)
 
+// blocks of a grid-stride launch over n work items
+inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
+    size_t g = (n + per_block - 1) / per_block;
+    if (g > (size_t)cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+// torch slices can start anywhere: a kernel takes its 16-byte accesses only when every stream it touches passes this
+inline bool vd_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 union U4H8 {
     uint4 u;
     f16x8 h;

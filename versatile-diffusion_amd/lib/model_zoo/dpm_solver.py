@@ -149,15 +149,18 @@ class DPMSolverSampler(DDIMSampler):
     def _extra_static(self, x):
         return {"x0_hist": torch.empty(x.shape, device=x.device, dtype=torch.float32)}
 
-    def _update_static(self, bufs, eps, guided):
+    def _solver_update(self, bufs, eps, guided):
         ops.cfg_dpmpp_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], guided=guided, x_next=bufs["xs"],
                                pred_x0=bufs["p0"])
+
+    def _update_static(self, bufs, eps, guided):
+        self._solver_update(bufs, eps, guided)
         if "mask" in bufs:      # inpainting: the history keeps the raw data prediction, only the latent is blended
             self._blend_static(bufs, bufs["xs"])
 
     def _step(self, *args, **kwargs):
         # the multistep update needs the history of the loop: there is no stand-alone single step (p_sample_ddim*)
-        raise NotImplementedError("DPMSolverSampler runs whole sample() loops on the GPU; it has no single-step API")
+        raise NotImplementedError("%s runs whole sample() loops on the GPU; it has no single-step API" % type(self).__name__)
 
 
 class DPMSolverSDESampler(DPMSolverSampler):
@@ -245,11 +248,6 @@ class DPMSolverSDESampler(DPMSolverSampler):
             st["seeds"].copy_(self._seeds)
         return super()._load_state(st, x, c_info_list, inpaint)
 
-    def _update_static(self, bufs, eps, guided):
+    def _solver_update(self, bufs, eps, guided):
         ops.cfg_dpmpp_sde_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["seeds"], bufs["rng"], guided=guided,
                                    x_next=bufs["xs"], pred_x0=bufs["p0"])
-        if "mask" in bufs:      # inpainting: blended after the update, like the 2M sampler
-            self._blend_static(bufs, bufs["xs"])
-
-    def _step(self, *args, **kwargs):
-        raise NotImplementedError("DPMSolverSDESampler runs whole sample() loops on the GPU; it has no single-step API")

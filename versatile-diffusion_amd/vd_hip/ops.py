@@ -910,12 +910,31 @@ def timestep_embedding(t, dim, max_period=10000.0):
     return out
 
 
-def cfg_ddim_step(x, eps, *, guided, guidance_scale, a_t, a_prev, sigma, sqrt_one_minus_at, noise=None,
-                  want_pred_x0=True):
-    _req(x, "x"); _req(eps, "eps"); _req(noise, "noise")
+def _eps_count(x, eps, guided):
+    """n = x.numel(), after checking that eps holds [e_uncond ; e_cond] (2n elements) when guided, else n."""
     n = x.numel()
     if eps.numel() != (2 * n if guided else n):
         raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
+    return n
+
+
+def _dpmpp_operands(x, eps, coef, x0_hist, guided, x_next, pred_x0):
+    """The operand checks both solver updates share; returns n = x.numel()."""
+    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x0_hist, "x0_hist", torch.float32)
+    _req(x_next, "x_next"); _req(pred_x0, "pred_x0")
+    n = _eps_count(x, eps, guided)
+    for t, name in ((x0_hist, "x0_hist"), (x_next, "x_next"), (pred_x0, "pred_x0")):
+        if t is not None and t.numel() != n:
+            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
+    if coef.numel() < 8:
+        raise VdHipError("coef has %d elements, expected 8" % coef.numel())
+    return n
+
+
+def cfg_ddim_step(x, eps, *, guided, guidance_scale, a_t, a_prev, sigma, sqrt_one_minus_at, noise=None,
+                  want_pred_x0=True):
+    _req(x, "x"); _req(eps, "eps"); _req(noise, "noise")
+    n = _eps_count(x, eps, guided)
     x_prev = torch.empty_like(x)
     pred_x0 = torch.empty_like(x) if want_pred_x0 else None
     _check(lib().vd_cfg_ddim_step_f16(_ptr(x), _ptr(eps), _ptr(noise), _ptr(x_prev), _ptr(pred_x0), n, 1 if guided else 0,
@@ -927,9 +946,7 @@ def cfg_ddim_step(x, eps, *, guided, guidance_scale, a_t, a_prev, sigma, sqrt_on
 def cfg_ddim_step_dev(x, eps, coef, *, guided, x_prev, pred_x0=None, noise=None):
     """CFG + DDIM update with the step scalars in a device fp32[6] tensor; writes into caller-owned buffers."""
     _req(x, "x"); _req(eps, "eps"); _req(noise, "noise"); _req(coef, "coef", torch.float32); _req(x_prev, "x_prev"); _req(pred_x0, "pred_x0")
-    n = x.numel()
-    if eps.numel() != (2 * n if guided else n):
-        raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
+    n = _eps_count(x, eps, guided)
     _check(lib().vd_cfg_ddim_step_dev_f16(_ptr(x), _ptr(eps), _ptr(noise), _ptr(x_prev), _ptr(pred_x0), n,
                                           1 if guided else 0, _ptr(coef), _stream()))
     return x_prev, pred_x0
@@ -938,16 +955,7 @@ def cfg_ddim_step_dev(x, eps, coef, *, guided, x_prev, pred_x0=None, noise=None)
 def cfg_dpmpp_step_dev(x, eps, coef, x0_hist, *, guided, x_next, pred_x0=None):
     """CFG + DPM-Solver++(2M) update with the step scalars in a device fp32[8] tensor (dpm_solver.dpmpp_coef_table rows);
     reads and rewrites the fp32 data-prediction history `x0_hist`, writes into caller-owned buffers (x_next may be x)."""
-    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x0_hist, "x0_hist", torch.float32)
-    _req(x_next, "x_next"); _req(pred_x0, "pred_x0")
-    n = x.numel()
-    if eps.numel() != (2 * n if guided else n):
-        raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
-    for t, name in ((x0_hist, "x0_hist"), (x_next, "x_next"), (pred_x0, "pred_x0")):
-        if t is not None and t.numel() != n:
-            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
-    if coef.numel() < 8:
-        raise VdHipError("coef has %d elements, expected 8" % coef.numel())
+    n = _dpmpp_operands(x, eps, coef, x0_hist, guided, x_next, pred_x0)
     _check(lib().vd_cfg_dpmpp_step_dev_f16(_ptr(x), _ptr(eps), _ptr(x0_hist), _ptr(x_next), _ptr(pred_x0), n,
                                            1 if guided else 0, _ptr(coef), _stream()))
     return x_next, pred_x0
@@ -976,16 +984,8 @@ def philox_normal(seeds, shape, *, draw=0, stream=0, dtype=torch.float16, scale=
 def cfg_dpmpp_sde_step_dev(x, eps, coef, x0_hist, seeds, rng, *, guided, x_next, pred_x0=None):
     """cfg_dpmpp_step_dev plus coef[7] * z with z generated in the kernel (dpm_solver.dpmpp_sde_coef_table rows): seeds is a
     device int64 [B] (x is [B, ...], one seed per sample), rng a device int32 [2] = {draw, stream} of philox_normal."""
-    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x0_hist, "x0_hist", torch.float32)
-    _req(x_next, "x_next"); _req(pred_x0, "pred_x0"); _req(seeds, "seeds", torch.int64); _req(rng, "rng", torch.int32)
-    n = x.numel()
-    if eps.numel() != (2 * n if guided else n):
-        raise VdHipError("eps has %d elements, expected %d" % (eps.numel(), 2 * n if guided else n))
-    for t, name in ((x0_hist, "x0_hist"), (x_next, "x_next"), (pred_x0, "pred_x0")):
-        if t is not None and t.numel() != n:
-            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
-    if coef.numel() < 8:
-        raise VdHipError("coef has %d elements, expected 8" % coef.numel())
+    n = _dpmpp_operands(x, eps, coef, x0_hist, guided, x_next, pred_x0)
+    _req(seeds, "seeds", torch.int64); _req(rng, "rng", torch.int32)
     B = seeds.numel()
     if B < 1 or x.dim() < 1 or x.shape[0] != B:
         raise VdHipError("seeds has %d elements, expected one per sample of x %s" % (B, tuple(x.shape)))
