@@ -441,6 +441,41 @@ int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, float* x0_hist
                                   int64_t per_sample, int guided, const float* coef, const int64_t* seeds,
                                   const int* rng, hipStream_t stream);
 
+/* Guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4; diffusers'
+ * guidance_rescale): the guided prediction is scaled back towards the standard deviation of the conditional one.  For sample
+ * b with m = per_sample elements (its flattened [C, *spatial] latent), guidance scale s = coef[0] and weight phi in [0, 1]:
+ *   eg_i = fmaf(s, ec_i - eu_i, eu_i)            fp32, the same value the updates compute
+ *   V(v) = sum v_i^2 - (sum v_i)^2 / m           sums over the sample, accumulated in fp64 (an fp32 value squared is exact there)
+ *   r    = sqrt(max(V(ec), 0) / V(eg))           fp64; r = 1 if V(eg) <= 0, m == 1 or r is not finite
+ *   k_b  = (float)(phi * r + (1 - phi))          fp64 (the product rounded, then the sum), rounded once to fp32
+ *   e'_i = k_b * eg_i                            fp32; e' takes the place of e everywhere in the update
+ * The ratio of standard deviations does not depend on the estimator's ddof, so this is diffusers' rule; phi = 0 gives k_b = 1
+ * exactly.  eps = [e_uncond ; e_cond] (2n fp16), coef and phi in device memory (coef: the row the update reads, only coef[0] is
+ * read; phi: one float), kfac: fp32 [n / per_sample].  One block of 256 lanes reduces a sample, whatever the batch, in an order
+ * that depends on per_sample alone (per-lane fp64 sums, a fixed butterfly over the wave, the waves added in order; no atomics),
+ * so k_b is a pure function of the sample's e_u and e_c, s and phi: the same bits for any batch size, batch position, alignment
+ * (16-byte loads when both halves of the sample are 16-byte aligned, else 2-byte loads of the same elements), graph or rank.
+ * Any per_sample.  Does not allocate or synchronise (capturable).  Returns < 0 for null pointers, n or per_sample <= 0, or n
+ * not a multiple of per_sample. */
+int vd_cfg_rescale_factor_f16(const void* eps, int64_t n, int64_t per_sample, const float* coef, const float* phi,
+                              float* kfac, hipStream_t stream);
+
+/* The fused updates with the guidance rescale: the sibling entry point (same name without _rs) with e' = kfac[i / per_sample] * e
+ * in the place of e -- one fp32 multiply right after e; everything after it follows the sibling's rounding rule, and with every
+ * kfac[b] == 1.0f the outputs are the sibling's bits.  The same kernels, instantiated with the multiply.  kfac: fp32
+ * [n / per_sample] in device memory (vd_cfg_rescale_factor_f16).  Return < 0 for the sibling's errors, a null kfac,
+ * per_sample <= 0, n not a multiple of per_sample, and guided == 0 (there is nothing to rescale). */
+int vd_cfg_ddim_step_rs_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0, int64_t n,
+                            int64_t per_sample, int guided, float guidance_scale, float a_t, float a_prev, float sigma,
+                            float sqrt_one_minus_at, const float* kfac, hipStream_t stream);
+int vd_cfg_ddim_step_dev_rs_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0, int64_t n,
+                                int64_t per_sample, int guided, const float* coef, const float* kfac, hipStream_t stream);
+int vd_cfg_dpmpp_step_dev_rs_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
+                                 int64_t per_sample, int guided, const float* coef, const float* kfac, hipStream_t stream);
+int vd_cfg_dpmpp_sde_step_dev_rs_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n,
+                                     int64_t per_sample, int guided, const float* coef, const int64_t* seeds, const int* rng,
+                                     const float* kfac, hipStream_t stream);
+
 /* Masked blend of blended latent diffusion (inpainting; not in the reference), after a sampler step lands on a_prev:
  *   out = m x + (1 - m) (ca x0 + cn noise),  coef[2] = {ca, cn} = {sqrt(a_prev), sqrt(1 - a_prev)} (or {1, 0} on the
  *   last step) in device memory, fp32 math, one fp16 rounding.

@@ -53,9 +53,14 @@ struct DdimCoef { float v[6]; };
 __device__ __forceinline__ float ddim_coef(const DdimCoef& c, int k) { return c.v[k]; }
 __device__ __forceinline__ float ddim_coef(const float* c, int k) { return c[k]; }
 
-template <typename Coef>
+// Guidance rescale (include/vd_hip.h, vd_cfg_rescale_factor_f16): RESCALE = true multiplies the guided prediction by its
+// sample's factor kfac[i / per_sample] (one fp32 multiply right after e); empty without it, so those instances take no factors.
+template <bool RESCALE> struct DdimRescale {};
+template <> struct DdimRescale<true> { const float* kfac; size_t per_sample; };
+
+template <typename Coef, bool RESCALE>
 __global__ void cfg_ddim_kernel(const f16* x, const f16* eps, const f16* noise, f16* x_prev, f16* pred_x0, size_t n,
-                                int guided, Coef coef) {
+                                int guided, Coef coef, DdimRescale<RESCALE> rs) {
     const float s = ddim_coef(coef, 0), rsqrt_at = ddim_coef(coef, 1), sqrt_aprev = ddim_coef(coef, 2),
                 dir_coef = ddim_coef(coef, 3), sigma = ddim_coef(coef, 4), sqrt_1mat = ddim_coef(coef, 5);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -64,11 +69,94 @@ __global__ void cfg_ddim_kernel(const f16* x, const f16* eps, const f16* noise, 
             const float ec = (float)eps[n + i];
             e = e + s * (ec - e);
         }
+        if constexpr (RESCALE) e = rs.kfac[i / rs.per_sample] * e;
         const float p0 = ((float)x[i] - sqrt_1mat * e) * rsqrt_at;
         float xp = sqrt_aprev * p0 + dir_coef * e;
         if (noise != nullptr) xp += sigma * (float)noise[i];
         x_prev[i] = (f16)xp;
         if (pred_x0 != nullptr) pred_x0[i] = (f16)p0;
+    }
+}
+
+// The factor of the guidance rescale, one per sample (contract: include/vd_hip.h).  A sample is always reduced by ONE block of
+// 256 lanes, whatever the batch: lane t takes the groups of 8 elements t, t + 256, ... of the sample (indices relative to the
+// sample's start) in order, then element 8 (m / 8) + t of the last partial group; four fp64 sums per lane (sum and sum of
+// squares of e_c and of the guided e), a fixed butterfly over the wave, then the four waves' sums added in wave order by lane 0.
+// Which lane adds which element in which order depends on nothing but m, so a sample's factor has the same bits wherever it
+// runs; the 16-byte loads (both halves of THIS sample 16-byte aligned, uniform over the block) and the 2-byte loads read the
+// same elements into the same sums.  A block walks samples blockIdx.x, blockIdx.x + gridDim.x, ...
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct RescaleSums {
+    double c1 = 0.0, c2 = 0.0, g1 = 0.0, g2 = 0.0;
+    __device__ __forceinline__ void add(float eu, float ec, float s) {
+        const float eg = fmaf(s, ec - eu, eu);          // the value the update computes
+        const double c = (double)ec, g = (double)eg;    // an fp32 value squared is exact in fp64
+        c1 += c;
+        c2 += c * c;
+        g1 += g;
+        g2 += g * g;
+    }
+};
+
+__device__ __forceinline__ float rescale_factor(double c1, double c2, double g1, double g2, size_t m, float phi) {
+#pragma clang fp contract(off)
+    const double md = (double)m;
+    const double vc = c2 - c1 * c1 / md, vg = g2 - g1 * g1 / md;
+    double r = 1.0;
+    if (m > 1 && vg > 0.0) {
+        r = sqrt(fmax(vc, 0.0) / vg);
+        if (!isfinite(r)) r = 1.0;
+    }
+    const double p = (double)phi;
+    return (float)(p * r + (1.0 - p));
+}
+
+__global__ __launch_bounds__(256) void cfg_rescale_factor_kernel(const f16* eps, size_t n, size_t m, const float* coef,
+                                                                 const float* phi, float* kfac) {
+    __shared__ double part[4][4];
+    const float s = coef[0];
+    const size_t B = n / m, groups = m / 8;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (size_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const f16* eu = eps + b * m;
+        const f16* ec = eu + n;
+        const bool vec = (((uintptr_t)eu | (uintptr_t)ec) & 15) == 0;
+        RescaleSums acc;
+        for (size_t g = tid; g < groups; g += 256) {
+            U4H8 u, c;
+            if (vec) {
+                u.u = reinterpret_cast<const uint4*>(eu)[g];
+                c.u = reinterpret_cast<const uint4*>(ec)[g];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    u.e[j] = eu[8 * g + j];
+                    c.e[j] = ec[8 * g + j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc.add((float)u.e[j], (float)c.e[j], s);
+        }
+        const size_t t = 8 * groups + (size_t)tid;
+        if (t < m) acc.add((float)eu[t], (float)ec[t], s);
+        const double w[4] = {wave_sum_f64(acc.c1), wave_sum_f64(acc.c2), wave_sum_f64(acc.g1), wave_sum_f64(acc.g2)};
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) part[q][wave] = w[q];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double tot[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tot[q] = ((part[q][0] + part[q][1]) + part[q][2]) + part[q][3];
+            kfac[b] = rescale_factor(tot[0], tot[1], tot[2], tot[3], m, phi[0]);
+        }
+        __syncthreads();
     }
 }
 
@@ -375,17 +463,57 @@ extern "C" int vd_cfg_ddim_step_f16(const void* x, const void* eps, const void* 
     float dir2 = 1.f - a_prev - sigma * sigma;
     if (dir2 < 0.f) dir2 = 0.f;
     const DdimCoef coef = {{guidance_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(dir2), sigma, sqrt_one_minus_at}};
-    hipLaunchKernelGGL(cfg_ddim_kernel<DdimCoef>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
-                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef);
+    hipLaunchKernelGGL((cfg_ddim_kernel<DdimCoef, false>), dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
+                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef,
+                       DdimRescale<false>{});
     return vd_check_launch("vd_cfg_ddim_step_f16");
 }
 
 extern "C" int vd_cfg_ddim_step_dev_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0,
                                         int64_t n, int guided, const float* coef, hipStream_t stream) {
     VD_REQUIRE(x && eps && x_prev && coef && n > 0, "vd_cfg_ddim_step_dev_f16: bad arguments");
-    hipLaunchKernelGGL(cfg_ddim_kernel<const float*>, dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
-                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef);
+    hipLaunchKernelGGL((cfg_ddim_kernel<const float*, false>), dim3(grid_for((size_t)n)), dim3(256), 0, stream,
+                       (const f16*)x, (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef,
+                       DdimRescale<false>{});
     return vd_check_launch("vd_cfg_ddim_step_dev_f16");
+}
+
+extern "C" int vd_cfg_ddim_step_rs_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0,
+                                       int64_t n, int64_t per_sample, int guided, float guidance_scale, float a_t,
+                                       float a_prev, float sigma, float sqrt_one_minus_at, const float* kfac,
+                                       hipStream_t stream) {
+    VD_REQUIRE(x && eps && x_prev && n > 0, "vd_cfg_ddim_step_rs_f16: bad arguments");
+    VD_REQUIRE(a_t > 0.f && a_prev >= 0.f, "vd_cfg_ddim_step_rs_f16: alphas must be positive");
+    if (const int rc = vd_rescale_args_ok("vd_cfg_ddim_step_rs_f16", n, per_sample, guided, kfac)) return rc;
+    float dir2 = 1.f - a_prev - sigma * sigma;
+    if (dir2 < 0.f) dir2 = 0.f;
+    const DdimCoef coef = {{guidance_scale, 1.0f / sqrtf(a_t), sqrtf(a_prev), sqrtf(dir2), sigma, sqrt_one_minus_at}};
+    hipLaunchKernelGGL((cfg_ddim_kernel<DdimCoef, true>), dim3(grid_for((size_t)n)), dim3(256), 0, stream, (const f16*)x,
+                       (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef,
+                       DdimRescale<true>{kfac, (size_t)per_sample});
+    return vd_check_launch("vd_cfg_ddim_step_rs_f16");
+}
+
+extern "C" int vd_cfg_ddim_step_dev_rs_f16(const void* x, const void* eps, const void* noise, void* x_prev, void* pred_x0,
+                                           int64_t n, int64_t per_sample, int guided, const float* coef, const float* kfac,
+                                           hipStream_t stream) {
+    VD_REQUIRE(x && eps && x_prev && coef && n > 0, "vd_cfg_ddim_step_dev_rs_f16: bad arguments");
+    if (const int rc = vd_rescale_args_ok("vd_cfg_ddim_step_dev_rs_f16", n, per_sample, guided, kfac)) return rc;
+    hipLaunchKernelGGL((cfg_ddim_kernel<const float*, true>), dim3(grid_for((size_t)n)), dim3(256), 0, stream,
+                       (const f16*)x, (const f16*)eps, (const f16*)noise, (f16*)x_prev, (f16*)pred_x0, (size_t)n, guided, coef,
+                       DdimRescale<true>{kfac, (size_t)per_sample});
+    return vd_check_launch("vd_cfg_ddim_step_dev_rs_f16");
+}
+
+extern "C" int vd_cfg_rescale_factor_f16(const void* eps, int64_t n, int64_t per_sample, const float* coef, const float* phi,
+                                         float* kfac, hipStream_t stream) {
+    VD_REQUIRE(eps && coef && phi && kfac && n > 0 && per_sample > 0, "vd_cfg_rescale_factor_f16: bad arguments");
+    VD_REQUIRE(n % per_sample == 0, "vd_cfg_rescale_factor_f16: n = %lld is not a multiple of per_sample = %lld", (long long)n,
+               (long long)per_sample);
+    const int64_t B = n / per_sample;
+    hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3((unsigned)(B < 65536 ? B : 65536)), dim3(256), 0, stream,
+                       (const f16*)eps, (size_t)n, (size_t)per_sample, coef, phi, kfac);
+    return vd_check_launch("vd_cfg_rescale_factor_f16");
 }
 
 extern "C" int vd_masked_blend_f16(const void* x, const void* x0, const void* noise, const void* mask, void* out, int B,

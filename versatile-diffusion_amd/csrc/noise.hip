@@ -89,11 +89,13 @@ __global__ void philox_normal_kernel(const int64_t* seeds, T* out, int B, size_t
 // fused in both forms.  Which element takes which form: the rule above cfg_dpmpp_dev_kernel.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <bool SPLIT>
+// RESCALE (guidance rescale, vd_cfg_rescale_factor_f16): e' = k e, one fp32 multiply right after e, takes e's place.
+template <bool SPLIT, bool RESCALE = false>
 __device__ __forceinline__ float dpmpp_elem_exact(float x, float eu, float ec, float h, int guided, bool second, float s,
                                                   float rsqrt_at, float sqrt_1mat, float ratio, float c_d, float w_cur,
-                                                  float w_prev, float& x0) {
-    const float e = guided ? fmaf(s, ec - eu, eu) : eu;
+                                                  float w_prev, float& x0, float k = 1.f) {
+    const float eg = guided ? fmaf(s, ec - eu, eu) : eu;
+    const float e = RESCALE ? k * eg : eg;
     x0 = fmaf(-sqrt_1mat, e, x) * rsqrt_at;
     if (SPLIT) {
         const f32x2 pd = f32x2{w_cur, w_prev} * f32x2{x0, h};
@@ -119,6 +121,10 @@ __device__ __forceinline__ f16 round_f16(float v) {
 template <bool NOISE> struct StepNoise {};
 template <> struct StepNoise<true> { const int64_t* seeds; const int* rng; size_t per_sample; };
 
+// the guidance rescale of a step: kfac[i / per_sample] multiplies the guided prediction of element i.  Empty without it.
+template <bool RESCALE> struct StepRescale {};
+template <> struct StepRescale<true> { const float* kfac; size_t per_sample; };
+
 // CFG combine + DPM-Solver++(2M) multistep update, step scalars in device memory (one captured graph serves all steps):
 // coef = {guidance scale, 1/sqrt(a_t), sqrt(1 - a_t), sigma_next / sigma_t, c_d, w_cur, w_prev, c_z}, then x0_hist = x0 (fp32).
 // w_prev == 0 (first-order rows) never reads x0_hist: it is uninitialised on the first step of a call.  x_next may alias x
@@ -135,9 +141,11 @@ template <> struct StepNoise<true> { const int64_t* seeds; const int* rng; size_
 //   elements of the scalar loop without noise      the two products of D and of x_next are rounded, then added (SPLIT = true)
 //   elements that get noise, on either loop        fused (SPLIT = false), then x_next = fma(c_z, z, x_next)
 // and x_next, pred_x0 are those fp32 values rounded to fp16 (round_f16), never a sum rounded straight to fp16.
-template <bool VEC, bool NOISE>
+// RESCALE = true (the _rs entry points): e' = kfac[i / rs.per_sample] * e takes e's place, everything after it as above.  A lane
+// of the 16-byte loop whose 8 elements do not lie in one sample (rs.per_sample % 8 != 0) looks the factor up per element.
+template <bool VEC, bool NOISE, bool RESCALE>
 __global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_hist, f16* x_next, f16* pred_x0, size_t n,
-                                     int guided, const float* coef, StepNoise<NOISE> src) {
+                                     int guided, const float* coef, StepNoise<NOISE> src, StepRescale<RESCALE> rs) {
     const float s = coef[0], rsqrt_at = coef[1], sqrt_1mat = coef[2], ratio = coef[3], c_d = coef[4], w_cur = coef[5],
                 w_prev = coef[6];
     const bool second = w_prev != 0.f;          // uniform over the grid
@@ -176,10 +184,23 @@ __global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_his
                 philox_normal4(key, j + 1u, draw, stream, z + 4);
             }
         }
+        float kf[8];
+        if constexpr (RESCALE) {
+            const size_t e0 = 8 * i, b0 = e0 / rs.per_sample;
+            if (e0 - b0 * rs.per_sample + 8 <= rs.per_sample) {
+                const float k = rs.kfac[b0];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) kf[j] = k;
+            } else {                                    // the lane straddles samples (any number of them: per_sample < 8)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) kf[j] = rs.kfac[(e0 + j) / rs.per_sample];
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float xn = dpmpp_elem_exact<false>((float)xv.e[j], (float)eu.e[j], guided ? (float)ec.e[j] : 0.f, h[j], guided,
-                                               second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0[j]);
+            float xn = dpmpp_elem_exact<false, RESCALE>((float)xv.e[j], (float)eu.e[j], guided ? (float)ec.e[j] : 0.f, h[j],
+                                                        guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev,
+                                                        x0[j], RESCALE ? kf[j] : 1.f);
             if (noisy) xn = fmaf(c_z, z[j], xn);
             xo.e[j] = round_f16(xn);
             po.e[j] = round_f16(x0[j]);
@@ -191,12 +212,15 @@ __global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_his
     }
     for (size_t i = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xf = (float)x[i], euf = (float)eps[i], ecf = guided ? (float)eps_c[i] : 0.f, hf = second ? x0_hist[i] : 0.f;
-        float x0, xn;
+        float x0, xn, k = 1.f;
+        if constexpr (RESCALE) k = rs.kfac[i / rs.per_sample];
         if (!noisy) {
-            xn = dpmpp_elem_exact<true>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
+            xn = dpmpp_elem_exact<true, RESCALE>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur,
+                                                 w_prev, x0, k);
         } else if constexpr (NOISE) {
             const size_t b = i / src.per_sample;
-            xn = dpmpp_elem_exact<false>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur, w_prev, x0);
+            xn = dpmpp_elem_exact<false, RESCALE>(xf, euf, ecf, hf, guided, second, s, rsqrt_at, sqrt_1mat, ratio, c_d, w_cur,
+                                                  w_prev, x0, k);
             xn = fmaf(c_z, philox_normal1(philox_key(src.seeds, b), i - b * src.per_sample, draw, stream), xn);
         }
         x_next[i] = round_f16(xn);
@@ -208,18 +232,18 @@ __global__ void cfg_dpmpp_dev_kernel(const f16* x, const f16* eps, float* x0_his
 // Both entry points' launch.  The alignment rule: 16-byte lanes only when every stream (both eps halves included) is aligned
 // (torch slices can start anywhere).  lanes8: a lane of the aligned kernel takes 8 elements (sizes the grid; whether a noisy
 // step can use the lanes, per_sample % 8 == 0, is the kernel's call).
-template <bool NOISE>
+template <bool NOISE, bool RESCALE>
 void launch_dpmpp(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0, int64_t n, int guided,
-                  const float* coef, bool lanes8, StepNoise<NOISE> src, hipStream_t stream) {
+                  const float* coef, bool lanes8, StepNoise<NOISE> src, StepRescale<RESCALE> rs, hipStream_t stream) {
     const bool vec = vd_aligned16(x) && vd_aligned16(eps) && (!guided || vd_aligned16((const f16*)eps + n)) &&
                      vd_aligned16(x0_hist) && vd_aligned16(x_next) && (pred_x0 == nullptr || vd_aligned16(pred_x0));
     const int grid = grid_for(vec && lanes8 ? (size_t)(n + 7) / 8 : (size_t)n);
     if (vec)
-        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<true, NOISE>), dim3(grid), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
-                           x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src);
+        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<true, NOISE, RESCALE>), dim3(grid), dim3(256), 0, stream, (const f16*)x,
+                           (const f16*)eps, x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src, rs);
     else
-        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<false, NOISE>), dim3(grid), dim3(256), 0, stream, (const f16*)x, (const f16*)eps,
-                           x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src);
+        hipLaunchKernelGGL((cfg_dpmpp_dev_kernel<false, NOISE, RESCALE>), dim3(grid), dim3(256), 0, stream, (const f16*)x,
+                           (const f16*)eps, x0_hist, (f16*)x_next, (f16*)pred_x0, (size_t)n, guided, coef, src, rs);
 }
 
 }  // namespace
@@ -242,8 +266,19 @@ extern "C" int vd_philox_normal(const int64_t* seeds, void* out, int out_is_f32,
 extern "C" int vd_cfg_dpmpp_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
                                          int64_t n, int guided, const float* coef, hipStream_t stream) {
     VD_REQUIRE(x && eps && x0_hist && x_next && coef && n > 0, "vd_cfg_dpmpp_step_dev_f16: bad arguments");
-    launch_dpmpp<false>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, true, StepNoise<false>{}, stream);
+    launch_dpmpp<false, false>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, true, StepNoise<false>{},
+                               StepRescale<false>{}, stream);
     return vd_check_launch("vd_cfg_dpmpp_step_dev_f16");
+}
+
+extern "C" int vd_cfg_dpmpp_step_dev_rs_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
+                                            int64_t n, int64_t per_sample, int guided, const float* coef, const float* kfac,
+                                            hipStream_t stream) {
+    VD_REQUIRE(x && eps && x0_hist && x_next && coef && n > 0, "vd_cfg_dpmpp_step_dev_rs_f16: bad arguments");
+    if (const int rc = vd_rescale_args_ok("vd_cfg_dpmpp_step_dev_rs_f16", n, per_sample, guided, kfac)) return rc;
+    launch_dpmpp<false, true>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, true, StepNoise<false>{},
+                              StepRescale<true>{kfac, (size_t)per_sample}, stream);
+    return vd_check_launch("vd_cfg_dpmpp_step_dev_rs_f16");
 }
 
 extern "C" int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
@@ -255,7 +290,21 @@ extern "C" int vd_cfg_dpmpp_sde_step_dev_f16(const void* x, const void* eps, flo
                (long long)n, (long long)per_sample);
     VD_REQUIRE((per_sample + 3) / 4 <= (int64_t)1 << 32,
                "vd_cfg_dpmpp_sde_step_dev_f16: per_sample %lld exceeds the 32-bit block counter", (long long)per_sample);
-    launch_dpmpp<true>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, per_sample % 8 == 0,
-                       StepNoise<true>{seeds, rng, (size_t)per_sample}, stream);
+    launch_dpmpp<true, false>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, per_sample % 8 == 0,
+                              StepNoise<true>{seeds, rng, (size_t)per_sample}, StepRescale<false>{}, stream);
     return vd_check_launch("vd_cfg_dpmpp_sde_step_dev_f16");
+}
+
+extern "C" int vd_cfg_dpmpp_sde_step_dev_rs_f16(const void* x, const void* eps, float* x0_hist, void* x_next, void* pred_x0,
+                                                int64_t n, int64_t per_sample, int guided, const float* coef,
+                                                const int64_t* seeds, const int* rng, const float* kfac, hipStream_t stream) {
+    VD_REQUIRE(x && eps && x0_hist && x_next && coef && seeds && rng && n > 0 && per_sample > 0,
+               "vd_cfg_dpmpp_sde_step_dev_rs_f16: bad arguments");
+    if (const int rc = vd_rescale_args_ok("vd_cfg_dpmpp_sde_step_dev_rs_f16", n, per_sample, guided, kfac)) return rc;
+    VD_REQUIRE((per_sample + 3) / 4 <= (int64_t)1 << 32,
+               "vd_cfg_dpmpp_sde_step_dev_rs_f16: per_sample %lld exceeds the 32-bit block counter", (long long)per_sample);
+    launch_dpmpp<true, true>(x, eps, x0_hist, x_next, pred_x0, n, guided, coef, per_sample % 8 == 0,
+                             StepNoise<true>{seeds, rng, (size_t)per_sample}, StepRescale<true>{kfac, (size_t)per_sample},
+                             stream);
+    return vd_check_launch("vd_cfg_dpmpp_sde_step_dev_rs_f16");
 }

@@ -27,6 +27,15 @@ int vd_check_launch(const char* what);
         }                                     \
     } while (0)
 
+// the operand rules the guidance-rescaled updates (vd_cfg_*_rs_f16) share; what: the entry point's name
+inline int vd_rescale_args_ok(const char* what, int64_t n, int64_t per_sample, int guided, const float* kfac) {
+    VD_REQUIRE(kfac && per_sample > 0, "%s: bad arguments", what);
+    VD_REQUIRE(guided != 0, "%s: the guidance rescale needs a guided step (eps = [e_uncond ; e_cond])", what);
+    VD_REQUIRE(n % per_sample == 0, "%s: n = %lld is not a multiple of per_sample = %lld", what, (long long)n,
+               (long long)per_sample);
+    return VD_OK;
+}
+
 // blocks of a grid-stride launch over n work items
 inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
     size_t g = (n + per_block - 1) / per_block;

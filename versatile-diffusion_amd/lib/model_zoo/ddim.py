@@ -8,6 +8,9 @@ and -- because every launch goes to torch's current stream with static shapes --
 ~450 kernel launches) is captured once into a HIP graph and replayed for the remaining steps; between replays the host
 only refreshes a 6-float coefficient vector and the timestep tensor.  Set VD_DDIM_GRAPH=0 to run every step eagerly.
 """
+import contextlib
+import gc
+import numbers
 import os
 import threading
 
@@ -51,6 +54,74 @@ def _inpaint_args(x_info, shape):
     if mask.shape[0] not in (1, shape[0]):
         raise ValueError("inpaint_mask has batch %d, expected 1 or %d" % (mask.shape[0], shape[0]))
     return True
+
+
+def cfg_guided_eps(eps, scale):
+    """float64 [B, ...]: the guided prediction eg = fmaf(s, ec - eu, eu) of eps = [e_uncond ; e_cond] ([2B, ...]) as the fused
+    updates form it in fp32 -- the difference rounded to fp32, the guidance scale rounded to fp32, the product-sum rounded to
+    fp32 once (formed in float64, where the product of two fp32 values is exact)."""
+    eu, ec = eps.detach().float().chunk(2)
+    s = float(np.float32(scale))
+    return (s * (ec - eu).double() + eu.double()).float().double()
+
+
+def cfg_rescale_factors(eps, scale, phi):
+    """float64 [B]: the guidance-rescale factors of eps = [e_uncond ; e_cond] ([2B, ...]) before their rounding to fp32, a plain
+    torch statement of the contract in include/vd_hip.h (Lin et al. 2023, section 3.4; diffusers' guidance_rescale):
+
+        eg = cfg_guided_eps(eps, scale);  V(v) = sum v^2 - (sum v)^2 / m  over the sample's m elements, in float64
+        r = sqrt(max(V(ec), 0) / V(eg)), or 1 if V(eg) <= 0, m == 1 or r is not finite;  k = phi r + (1 - phi)
+
+    with phi rounded to fp32 first (the samplers keep it in an fp32 device buffer).  The kernel's factor
+    (ops.cfg_rescale_factor, intermediates['guidance_rescale']) is k.float(); the update then uses e' = k eg in place of eg."""
+    ec = eps.detach().float().chunk(2)[1].double().flatten(1)
+    eg = cfg_guided_eps(eps, scale).flatten(1)
+    m = ec.shape[1]
+    var = lambda v: (v * v).sum(1) - v.sum(1) ** 2 / m
+    vc, vg = var(ec), var(eg)
+    ok = vg > 0 if m > 1 else torch.zeros_like(vg, dtype=torch.bool)
+    r = torch.sqrt(vc.clamp(min=0) / torch.where(ok, vg, torch.ones_like(vg)))
+    r = torch.where(ok & torch.isfinite(r), r, torch.ones_like(r))
+    p = float(np.float32(phi))
+    return p * r + (1.0 - p)
+
+
+def _rescale_arg(c_info_list):
+    """The contexts' 'guidance_rescale' (extension key, default 0 = off) as a float, validated: ValueError unless it is a real
+    number in [0, 1] that all contexts of the call agree on.  Touches no device."""
+    phis = []
+    for ci in c_info_list:
+        value = ci.get("guidance_rescale", 0.)
+        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not 0. <= float(value) <= 1.:
+            raise ValueError("c_info['guidance_rescale'] must be a real number in [0, 1], got %r" % (value,))
+        phis.append(float(value))
+    if any(p != phis[0] for p in phis):
+        raise ValueError("A different guidance_rescale between different context is not allowed, got %r" % (phis,))
+    return phis[0]
+
+
+_gc_lock = threading.Lock()
+_gc_holds = [0, False]      # captures in progress in this process; whether the collector was on when the first began
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """Python's cyclic collector stays off while a step is being captured, in any thread: a collection that frees a dropped
+    sampler's kept graph runs torch's graph destructor, which synchronises the device -- not allowed while a stream is
+    capturing, and an error thrown from a destructor ends the process.  The collector's setting is process-wide, so captures
+    are counted: the first switches it off, the last restores it.  Garbage made meanwhile waits for the next collection."""
+    with _gc_lock:
+        if _gc_holds[0] == 0:
+            _gc_holds[1] = gc.isenabled()
+            gc.disable()
+        _gc_holds[0] += 1
+    try:
+        yield
+    finally:
+        with _gc_lock:
+            _gc_holds[0] -= 1
+            if _gc_holds[0] == 0 and _gc_holds[1]:
+                gc.enable()
 
 
 class DDIMSampler(object):
@@ -134,7 +205,10 @@ class DDIMSampler(object):
 
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
         masked = _inpaint_args(x_info, shape)
+        # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
+        # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
+        c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list)
         dtype = c_info_list[0]["conditioning"].dtype
         x_info["x"], timesteps, blend_noise = self._start_latent(shape, x_info, masked, device, dtype)
         inpaint = None
@@ -144,8 +218,6 @@ class DDIMSampler(object):
             inpaint = {"x0": x_info["x0"].to(**f16).contiguous(), "mask": x_info["inpaint_mask"].to(**f16).contiguous(),
                        "noise": blend_noise.to(**f16).contiguous(),
                        "table": torch.from_numpy(inpaint_blend_table(self.alphas_cumprod, timesteps)).to(device)}
-        # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop
-        c_info_list, guided, scale = self._cfg_contexts(c_info_list)
 
         total_steps = timesteps.shape[0]
         x = x_info["x"].to(torch.float16).contiguous()
@@ -154,20 +226,25 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint)
+                                                 inpaint, phi)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
+            if phi > 0.:
+                intermediates["guidance_rescale"] = []
             for ci in c_info_list:
                 ci["kv_cache"] = {}
+            rescale = self._rescale_scalars(scale, phi, x.device)         # once per call, not per step
             for i, step in enumerate(np.flip(timesteps)):
                 index = total_steps - i - 1
-                x, pred_x0 = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
-                                        noise_dropout=noise_dropout)
+                x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
+                                              noise_dropout=noise_dropout, rescale=rescale)
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
                     intermediates["pred_xt"].append(x.to(dtype))
                     intermediates["pred_x0"].append(pred_x0.to(dtype))
+                    if kfac is not None:
+                        intermediates["guidance_rescale"].append(kfac)
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
 
@@ -193,19 +270,24 @@ class DDIMSampler(object):
         return x, timesteps, x if noise is None else noise
 
     def _cfg_contexts(self, c_info_list):
-        """(copies, guided, scale): shallow copies of the contexts with 'c', the batch the UNet sees ([uncond ; cond] under
+        """(copies, guided, scale, phi): shallow copies of the contexts with 'c', the batch the UNet sees ([uncond ; cond] under
         guidance), on the model's device.  The samplers work on the copies: 'c' (possibly a static buffer the captured graph
-        reads) and 'kv_cache' never appear in the caller's dicts."""
+        reads) and 'kv_cache' never appear in the caller's dicts.  phi = c_info['guidance_rescale'] (extension key, default
+        0 = off; cfg_rescale_factors): ValueError unless it is a real number in [0, 1] that all contexts agree on; an unguided
+        call (scale == 1) ignores it, phi = 0."""
         scale = c_info_list[0]["unconditional_guidance_scale"]
         for ci in c_info_list:
             assert ci["unconditional_guidance_scale"] == scale, \
                 "A different unconditional guidance scale between different context is not allowed!"
+        phi = _rescale_arg(c_info_list)
         guided = scale != 1.
+        if not guided:
+            phi = 0.
         copies = [dict(ci) for ci in c_info_list]
         for ci in copies:
             c = torch.cat([ci["unconditional_conditioning"], ci["conditioning"]]) if guided else ci["conditioning"]
             ci["c"] = c.to(self.model.device)
-        return copies, guided, scale
+        return copies, guided, scale, phi
 
     def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
@@ -229,9 +311,11 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0.):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
-        projections, the sampler's own buffers (_extra_static) and, when inpainting, x0 / noise / mask / blend; and the graph."""
+        projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
+        rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
+        (fp32 [B], written by every step); and the graph."""
         nb = (2 if guided else 1) * x.shape[0]
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
@@ -239,12 +323,15 @@ class DDIMSampler(object):
               "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
               "kv": [dict() for _ in c_info_list], "graph": None}
         st.update(self._extra_static(x))
+        if rescale > 0.:
+            st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
+                      kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
         if inpaint is not None:
             st.update({k: torch.empty_like(inpaint[k]) for k in ("x0", "noise", "mask")},
                       blend=torch.empty((2,), device=x.device, dtype=torch.float32))
         return st
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0.):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -256,23 +343,27 @@ class DDIMSampler(object):
         wv = hash(tuple((t.data_ptr(), t._version) for t in list(self.model.parameters()) + list(self.model.buffers())))
         # (emb_hoist is part of the key: a step graph captured with the hoisted time embedding reads st["embrow"], one captured
         # without it computes the embedding inside the step -- replaying either under the other setting would be silently wrong;
-        # so is inpainting with its mask batch: a graph captured with the blend reads the static x0 / noise / mask buffers)
+        # so is inpainting with its mask batch: a graph captured with the blend reads the static x0 / noise / mask buffers;
+        # and the guidance rescale (`rescale`: its weight), on or off whatever the positive weight: a graph captured with it
+        # launches the factor kernel and the rescaled update, one captured without it must keep giving the unrescaled bits)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
-               inpaint is not None, mask_batch)
+               inpaint is not None, mask_batch, rescale > 0.)
         st = self._static.pop(key, None)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale)
         self._static[key] = st                                 # most recently used last
         return st
 
-    def _load_state(self, st, x, c_info_list, inpaint):
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0.):
         """Copy this call's latent, contexts and inpainting tensors into the state and hand its context buffers and K/V caches to
         c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
         st["xs"].copy_(x)
+        if "phi" in st:
+            st["phi"].fill_(phi)
         if inpaint is not None:
             for k in ("x0", "noise", "mask"):
                 st[k].copy_(inpaint[k])
@@ -309,13 +400,16 @@ class DDIMSampler(object):
             st["embrow"] = torch.empty((emb_tab.shape[1],), device=emb_tab.device, dtype=torch.float16)
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
-    def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None):
+    def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
+                     phi=0.):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry.  Returns (final fp16 latent, intermediates)."""
         total_steps = timesteps.shape[0]
-        st = self._static_state(x, x_info, c_info_list, guided, single, inpaint) or self._new_state(x, c_info_list, guided, inpaint)
-        replay_first = self._load_state(st, x, c_info_list, inpaint)
+        rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale))
+        replay_first = self._load_state(st, x, c_info_list, inpaint, rescale)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
         steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
@@ -334,6 +428,8 @@ class DDIMSampler(object):
             torch.randn_like(st["xs"])
         rng_after = torch.cuda.get_rng_state(x.device)
         intermediates = {"pred_xt": [], "pred_x0": []}
+        if rescale > 0.:
+            intermediates["guidance_rescale"] = []
         for i in range(total_steps):
             index = total_steps - i - 1
             st["ts"].copy_(steps_dev[i].expand(st["ts"].shape[0]))       # device-side refresh, no host sync
@@ -357,6 +453,8 @@ class DDIMSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["pred_xt"].append(st["xs"].to(dtype).clone())
                 intermediates["pred_x0"].append(st["p0"].to(dtype).clone())
+                if rescale > 0.:
+                    intermediates["guidance_rescale"].append(st["kfac"].clone())
         torch.cuda.set_rng_state(rng_after, x.device)
         return st["xs"].clone(), intermediates
 
@@ -372,12 +470,23 @@ class DDIMSampler(object):
     def _update_static(self, bufs, eps, guided):
         """The update at the end of a static step: reads bufs["xs"] (latent), eps and bufs["coef"], leaves the next latent in
         bufs["xs"] and the data prediction in bufs["p0"].  Captured into the step graph with the UNet forward.  When inpainting
-        (bufs has "mask"), the latent that lands in bufs["xs"] is blended with the known region (_blend_static)."""
-        ops.cfg_ddim_step_dev(bufs["xs"], eps, bufs["coef"], guided=guided, x_prev=bufs["x_next"], pred_x0=bufs["p0"])
+        (bufs has "mask"), the latent that lands in bufs["xs"] is blended with the known region (_blend_static).  With the
+        guidance rescale (bufs has "kfac") the factor kernel runs first and the update multiplies by its factors."""
+        if "kfac" in bufs:
+            self._rescale_static(bufs, eps)
+            ops.cfg_ddim_step_dev_rs(bufs["xs"], eps, bufs["coef"], bufs["kfac"], guided=guided, x_prev=bufs["x_next"],
+                                     pred_x0=bufs["p0"])
+        else:
+            ops.cfg_ddim_step_dev(bufs["xs"], eps, bufs["coef"], guided=guided, x_prev=bufs["x_next"], pred_x0=bufs["p0"])
         if "mask" in bufs:
             self._blend_static(bufs, bufs["x_next"])          # in place of the copy: no extra launch
         else:
             bufs["xs"].copy_(bufs["x_next"])
+
+    @staticmethod
+    def _rescale_static(bufs, eps):
+        """bufs["kfac"] = the guidance-rescale factors of eps for the scale in bufs["coef"][0] and the weight bufs["phi"]."""
+        ops.cfg_rescale_factor(eps, bufs["coef"], bufs["phi"], bufs["xs"].numel() // bufs["xs"].shape[0], out=bufs["kfac"])
 
     @staticmethod
     def _blend_static(bufs, x):
@@ -385,6 +494,10 @@ class DDIMSampler(object):
         ops.masked_blend(x, bufs["x0"], bufs["noise"], bufs["mask"], bufs["blend"], out=bufs["xs"])
 
     def _capture(self, body):
+        with _no_gc():
+            return self._capture_step(body)
+
+    def _capture_step(self, body):
         try:
             g = torch.cuda.CUDAGraph()
             s = torch.cuda.Stream()
@@ -400,8 +513,9 @@ class DDIMSampler(object):
             self.use_graph = False
             return None
 
-    def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0.):
-        """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]."""
+    def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None):
+        """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
+        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars."""
         t_in = torch.full(((2 if guided else 1) * x.shape[0],), step, device=x.device, dtype=torch.long)
         eps = self._eps(x_info, x, t_in, c_info_list, guided, single)
         sigma = float(self.ddim_sigmas[index])
@@ -416,10 +530,23 @@ class DDIMSampler(object):
             noise = noise if temperature == 1. else (noise.float() * temperature).to(torch.float16)
         else:
             noise = None
-        return ops.cfg_ddim_step(x, eps.contiguous(), guided=guided, guidance_scale=float(scale),
-                                 a_t=float(self.ddim_alphas[index]), a_prev=float(self.ddim_alphas_prev[index]),
-                                 sigma=sigma, sqrt_one_minus_at=float(self.ddim_sqrt_one_minus_alphas[index]),
-                                 noise=noise)
+        scalars = dict(guided=guided, guidance_scale=float(scale), a_t=float(self.ddim_alphas[index]),
+                       a_prev=float(self.ddim_alphas_prev[index]), sigma=sigma,
+                       sqrt_one_minus_at=float(self.ddim_sqrt_one_minus_alphas[index]), noise=noise)
+        eps = eps.contiguous()
+        if rescale is None:
+            return ops.cfg_ddim_step(x, eps, **scalars) + (None,)
+        kfac = ops.cfg_rescale_factor(eps, rescale[0], rescale[1], x.numel() // x.shape[0])
+        return ops.cfg_ddim_step_rs(x, eps, kfac, **scalars) + (kfac,)
+
+    @staticmethod
+    def _rescale_scalars(scale, phi, device):
+        """(guidance scale, weight) as fp32 [1] device tensors for the eager steps' factor kernel; None when the rescale is off
+        (phi == 0, which _cfg_contexts also returns for an unguided call)."""
+        if not phi > 0.:
+            return None
+        f32 = dict(device=device, dtype=torch.float32)
+        return torch.full((1,), float(scale), **f32), torch.full((1,), float(phi), **f32)
 
     @torch.no_grad()
     def p_sample_ddim(self, x_info, c_info, t, index, repeat_noise=False, use_original_steps=False,
@@ -436,8 +563,9 @@ class DDIMSampler(object):
         if x_info.get("inpaint_mask") is not None:
             raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")
         assert not use_original_steps and not repeat_noise
-        cis, guided, scale = self._cfg_contexts(c_info_list)
+        cis, guided, scale, phi = self._cfg_contexts(c_info_list)
         x = x_info["x"]
-        xp, p0 = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
-                            temperature, single, noise_dropout=noise_dropout)
+        xp, p0, _ = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
+                               temperature, single, noise_dropout=noise_dropout,
+                               rescale=self._rescale_scalars(scale, phi, x.device))
         return xp.to(x.dtype), p0.to(x.dtype)

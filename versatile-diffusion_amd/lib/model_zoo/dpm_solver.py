@@ -150,8 +150,13 @@ class DPMSolverSampler(DDIMSampler):
         return {"x0_hist": torch.empty(x.shape, device=x.device, dtype=torch.float32)}
 
     def _solver_update(self, bufs, eps, guided):
-        ops.cfg_dpmpp_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], guided=guided, x_next=bufs["xs"],
-                               pred_x0=bufs["p0"])
+        if "kfac" in bufs:      # guidance rescale: the factor kernel, then the update that multiplies by its factors
+            self._rescale_static(bufs, eps)
+            ops.cfg_dpmpp_step_dev_rs(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["kfac"], guided=guided,
+                                      x_next=bufs["xs"], pred_x0=bufs["p0"])
+        else:
+            ops.cfg_dpmpp_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], guided=guided, x_next=bufs["xs"],
+                                   pred_x0=bufs["p0"])
 
     def _update_static(self, bufs, eps, guided):
         self._solver_update(bufs, eps, guided)
@@ -241,13 +246,18 @@ class DPMSolverSDESampler(DPMSolverSampler):
         return dict(super()._extra_static(x), seeds=torch.zeros((x.shape[0],), device=x.device, dtype=torch.int64),
                     rng=torch.zeros((2,), device=x.device, dtype=torch.int32))
 
-    def _load_state(self, st, x, c_info_list, inpaint):
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0.):
         if self._seeds is None:
             st["seeds"].zero_()          # eta = 0 without seeds: the noise coefficient is 0 and the seeds are not read
         else:
             st["seeds"].copy_(self._seeds)
-        return super()._load_state(st, x, c_info_list, inpaint)
+        return super()._load_state(st, x, c_info_list, inpaint, phi)
 
     def _solver_update(self, bufs, eps, guided):
-        ops.cfg_dpmpp_sde_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["seeds"], bufs["rng"], guided=guided,
-                                   x_next=bufs["xs"], pred_x0=bufs["p0"])
+        if "kfac" in bufs:
+            self._rescale_static(bufs, eps)
+            ops.cfg_dpmpp_sde_step_dev_rs(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["seeds"], bufs["rng"],
+                                          bufs["kfac"], guided=guided, x_next=bufs["xs"], pred_x0=bufs["p0"])
+        else:
+            ops.cfg_dpmpp_sde_step_dev(bufs["xs"], eps, bufs["coef"], bufs["x0_hist"], bufs["seeds"], bufs["rng"],
+                                       guided=guided, x_next=bufs["xs"], pred_x0=bufs["p0"])

@@ -91,7 +91,7 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 
 
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
-                      images=None, fidelity=0., device_generator=False, mask=None):
+                      images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -101,13 +101,17 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     images + mask: inpainting (not in the reference) -- `mask` is the pixel mask of this rank's `images` [n_local, 1, H, W]
     or a broadcast [1, 1, H, W] (1 = regenerate, 0 = keep), turned into the latent mask by app_ops.latent_mask(mode="max").
-    x0 is encoded as above also when fidelity == 0, and then the full schedule runs from x_T."""
+    x0 is encoded as above also when fidelity == 0, and then the full schedule runs from x_T.
+
+    guidance_rescale: the samplers' c_info['guidance_rescale'] (ddim.cfg_rescale_factors), set next to the scale; a sample's
+    factors do not depend on the rank or the slice it runs in."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
 
     def sample_fn(x_T, ctxs):
         for ci in ctxs:
             ci["unconditional_guidance_scale"] = guidance_scale
+            ci["guidance_rescale"] = guidance_rescale
         lshape = [x_T.shape[0]] + list(shape[1:])
         if images is not None and (fidelity > 0. or mask is not None):
             # every random number of this branch comes from a seeded FULL-batch draw sliced to this rank's samples, like

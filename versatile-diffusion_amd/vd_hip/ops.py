@@ -996,6 +996,94 @@ def cfg_dpmpp_sde_step_dev(x, eps, coef, x0_hist, seeds, rng, *, guided, x_next,
     return x_next, pred_x0
 
 
+def _per_sample(x, kfac, n):
+    """per_sample of a rescaled update: kfac is a device fp32 [B] with one factor per sample of x [B, ...]."""
+    _req(kfac, "kfac", torch.float32)
+    B = kfac.numel()
+    if B < 1 or x.dim() < 1 or x.shape[0] != B:
+        raise VdHipError("kfac has %d elements, expected one per sample of x %s" % (B, tuple(x.shape)))
+    return n // B
+
+
+def _req_guided(guided):
+    if not guided:
+        raise VdHipError("the guidance rescale needs a guided step (eps = [e_uncond ; e_cond])")
+
+
+def cfg_rescale_factor(eps, coef, phi, per_sample, out=None):
+    """The guidance-rescale factors k_b of include/vd_hip.h (vd_cfg_rescale_factor_f16): eps = [e_uncond ; e_cond] (fp16, 2n
+    elements), coef a device fp32 row whose first element is the guidance scale (the row the update reads), phi a device
+    fp32 [1], per_sample the elements of one sample; returns fp32 [n / per_sample] (`out` if given)."""
+    _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(phi, "phi", torch.float32)
+    per_sample = int(per_sample)
+    if eps.numel() < 2 or eps.numel() % 2:
+        raise VdHipError("eps has %d elements, expected [e_uncond ; e_cond]" % eps.numel())
+    n = eps.numel() // 2
+    if per_sample <= 0 or n % per_sample:
+        raise VdHipError("eps holds 2 x %d elements, not a multiple of per_sample = %d" % (n, per_sample))
+    if coef.numel() < 1 or phi.numel() < 1:
+        raise VdHipError("coef and phi must hold at least one element each")
+    if out is None:
+        out = torch.empty((n // per_sample,), dtype=torch.float32, device=eps.device)
+    _req(out, "out", torch.float32)
+    if out.numel() != n // per_sample:
+        raise VdHipError("out has %d elements, expected %d" % (out.numel(), n // per_sample))
+    _check(lib().vd_cfg_rescale_factor_f16(_ptr(eps), n, per_sample, _ptr(coef), _ptr(phi), _ptr(out), _stream()))
+    return out
+
+
+def cfg_ddim_step_rs(x, eps, kfac, *, guided, guidance_scale, a_t, a_prev, sigma, sqrt_one_minus_at, noise=None,
+                     want_pred_x0=True):
+    """cfg_ddim_step with the guidance rescale: e' = kfac[b] * e for sample b of x [B, ...] (kfac: cfg_rescale_factor)."""
+    _req(x, "x"); _req(eps, "eps"); _req(noise, "noise")
+    _req_guided(guided)
+    n = _eps_count(x, eps, guided)
+    per = _per_sample(x, kfac, n)
+    x_prev = torch.empty_like(x)
+    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
+    _check(lib().vd_cfg_ddim_step_rs_f16(_ptr(x), _ptr(eps), _ptr(noise), _ptr(x_prev), _ptr(pred_x0), n, per, 1,
+                                         float(guidance_scale), float(a_t), float(a_prev), float(sigma),
+                                         float(sqrt_one_minus_at), _ptr(kfac), _stream()))
+    return x_prev, pred_x0
+
+
+def cfg_ddim_step_dev_rs(x, eps, coef, kfac, *, guided, x_prev, pred_x0=None, noise=None):
+    """cfg_ddim_step_dev with the guidance rescale (kfac: device fp32 [B], one factor per sample of x)."""
+    _req(x, "x"); _req(eps, "eps"); _req(noise, "noise"); _req(coef, "coef", torch.float32); _req(x_prev, "x_prev"); _req(pred_x0, "pred_x0")
+    _req_guided(guided)
+    n = _eps_count(x, eps, guided)
+    per = _per_sample(x, kfac, n)
+    _check(lib().vd_cfg_ddim_step_dev_rs_f16(_ptr(x), _ptr(eps), _ptr(noise), _ptr(x_prev), _ptr(pred_x0), n, per, 1,
+                                             _ptr(coef), _ptr(kfac), _stream()))
+    return x_prev, pred_x0
+
+
+def cfg_dpmpp_step_dev_rs(x, eps, coef, x0_hist, kfac, *, guided, x_next, pred_x0=None):
+    """cfg_dpmpp_step_dev with the guidance rescale (kfac: device fp32 [B], one factor per sample of x)."""
+    _req_guided(guided)
+    n = _dpmpp_operands(x, eps, coef, x0_hist, guided, x_next, pred_x0)
+    per = _per_sample(x, kfac, n)
+    _check(lib().vd_cfg_dpmpp_step_dev_rs_f16(_ptr(x), _ptr(eps), _ptr(x0_hist), _ptr(x_next), _ptr(pred_x0), n, per, 1,
+                                              _ptr(coef), _ptr(kfac), _stream()))
+    return x_next, pred_x0
+
+
+def cfg_dpmpp_sde_step_dev_rs(x, eps, coef, x0_hist, seeds, rng, kfac, *, guided, x_next, pred_x0=None):
+    """cfg_dpmpp_sde_step_dev with the guidance rescale (kfac: device fp32 [B], one factor per sample of x)."""
+    _req_guided(guided)
+    n = _dpmpp_operands(x, eps, coef, x0_hist, guided, x_next, pred_x0)
+    _req(seeds, "seeds", torch.int64); _req(rng, "rng", torch.int32)
+    B = seeds.numel()
+    if B < 1 or x.dim() < 1 or x.shape[0] != B:
+        raise VdHipError("seeds has %d elements, expected one per sample of x %s" % (B, tuple(x.shape)))
+    if rng.numel() < 2:
+        raise VdHipError("rng has %d elements, expected 2" % rng.numel())
+    per = _per_sample(x, kfac, n)
+    _check(lib().vd_cfg_dpmpp_sde_step_dev_rs_f16(_ptr(x), _ptr(eps), _ptr(x0_hist), _ptr(x_next), _ptr(pred_x0), n, per, 1,
+                                                  _ptr(coef), _ptr(seeds), _ptr(rng), _ptr(kfac), _stream()))
+    return x_next, pred_x0
+
+
 def masked_blend(x, x0, noise, mask, coef, out=None):
     """Inpainting blend out = m x + (1 - m) (ca x0 + cn noise) with coef = device fp32 {ca, cn} (a row of
     ddim.inpaint_blend_table).  x, x0, noise: [B, C, *spatial]; mask: [Bm, 1, *spatial] or [Bm, *spatial] with Bm = 1 or
@@ -1250,7 +1338,8 @@ def _guarded(fn):
 
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
-              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
