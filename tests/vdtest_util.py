@@ -289,3 +289,52 @@ def exact_mismatch(out, ref, names, context="", limit=6):
 def assert_exact(out, ref, names, context=""):
     msg = exact_mismatch(out, ref, names, context)
     assert msg is None, msg
+
+
+# ---- per-element checks of the attention kernels: tests/attn_cases.py holds the case table --------------------------------------
+ATTN_REL = 2.0 ** -20     # the kernels' inexact steps are the fp32 1 / l and one fp32 product (<= 2^-24 each); eightfold margin
+ATTN_AXES = ("batch", "query", "head", "channel")
+
+
+def fp16_interval(ref, rel=ATTN_REL):
+    """(lo, hi) float64 arrays: the fp16 values of ref * (1 - rel) and ref * (1 + rel), smaller first (numpy rounds float64 to
+    fp16 directly, to nearest even).  Where `ref` is itself an fp16 value the interval is that value alone."""
+    r = np.asarray(torch.as_tensor(ref).detach().double().cpu().numpy(), np.float64)
+    a = (r * (1.0 - rel)).astype(np.float16).astype(np.float64)
+    b = (r * (1.0 + rel)).astype(np.float16).astype(np.float64)
+    return np.minimum(a, b), np.maximum(a, b)
+
+
+def attn_bad(out, ref, rel=ATTN_REL):
+    """bool array: the elements of `out` outside fp16_interval(ref, rel), NaN included."""
+    got = torch.as_tensor(out).detach().double().cpu().numpy()
+    lo, hi = fp16_interval(ref, rel)
+    return ~((got >= lo) & (got <= hi))
+
+
+def attn_mismatch(out, ref, context="", rel=ATTN_REL, win_key=None, qblock=128, wave_rows=32, wave_cols=None, limit=6):
+    """The acceptance rule of the exact attention tests on [batch, query, head, channel] arrays: an element passes if it lies
+    between fp16(ref * (1 - rel)) and fp16(ref * (1 + rel)) inclusive -- bit-for-bit equality where `ref` is an fp16 value,
+    "correctly rounded" otherwise.  None when every element passes, else a report: the number of failing elements, their extent
+    per axis, the first `limit` coordinates with got / expected and the selected key (win_key [batch, head, query], if given), and
+    the query block and wave of the first failure: query // qblock and (query % qblock) // wave_rows, or channel // wave_cols for
+    a kernel that splits the head dim over its waves."""
+    got = torch.as_tensor(out).detach().double().cpu().numpy()
+    refn = torch.as_tensor(ref).detach().double().cpu().numpy()
+    if got.shape != refn.shape:
+        return "%s: shape %s, expected %s" % (context, got.shape, refn.shape)
+    bad = attn_bad(got, refn, rel)
+    if not bad.any():
+        return None
+    idx = np.argwhere(bad)
+    lo, hi = fp16_interval(refn, rel)
+    lines = ["%s: %d of %d elements fail" % (context, idx.shape[0], refn.size)]
+    lines.append("  extent: " + ", ".join("%s %d..%d" % (n, idx[:, i].min(), idx[:, i].max()) for i, n in enumerate(ATTN_AXES)))
+    b, i, h, c = [int(x) for x in idx[0]]
+    wave = c // wave_cols if wave_cols else (i % qblock) // wave_rows
+    lines.append("  first failure: query block %d, wave %d" % (i // qblock, wave))
+    for b, i, h, c in idx[:limit].tolist():
+        sel = "" if win_key is None else ", selected key %d" % int(win_key[b][h][i])
+        want = "%.10g" % refn[b, i, h, c] if lo[b, i, h, c] == hi[b, i, h, c] else "%.10g (fp16 %g..%g)" % (refn[b, i, h, c], lo[b, i, h, c], hi[b, i, h, c])
+        lines.append("  (batch=%d, query=%d, head=%d, channel=%d): got %g, expected %s%s" % (b, i, h, c, got[b, i, h, c], want, sel))
+    return "\n".join(lines)
