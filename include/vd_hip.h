@@ -211,6 +211,7 @@ int vd_conv3x3_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 int vd_gemm_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 /* Development hook: kernel instance (0 = default) and the grid size the split over chunks aims for (256). Process-global. */
 int vd_conv3x3_wstream_set_variant(int variant, int target_blocks);
+/* (a tile_cfg that is not built is refused: non-zero return, table unchanged) */
 int vd_gemm_tune_set(int M, int N, int K, int ksize, int epi_class, int tile_cfg, int nsplit);
 int vd_gemm_tune_clear(void);
 

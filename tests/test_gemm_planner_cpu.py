@@ -319,3 +319,45 @@ def test_which_8x8_convolutions_run_without_a_split_and_which_launches_take_row_
     assert rs_ok(32768, 320, 2880, ks=3) == 0                   # halo-resident convolution: another epilogue
     assert rs_ok(2048, 1280, 5120, ws=True) in (0, 1)           # (whatever the planner picks, the answer is consistent with ...)
     assert rs_ok(8192, 644, 640) == 0                           # N % 8 != 0
+
+
+def test_tune_set_refuses_a_tile_that_is_not_built():
+    """vd_gemm_tune_set: an entry for a retired slot would fail inside the forward ("not instantiated"); it is refused at the
+    door, names the slot and leaves the table as it was -- the plan of that shape answers as if nothing had been set."""
+    from vd_hip.loader import lib
+    M, N, K = 2048, 1280, 5120
+    try:
+        assert lib().vd_gemm_tune_clear() == 0
+        before = plan(M, N, K)
+        for retired in (T256x256, T128x128q, T128x320q, 5, 6, 26):
+            assert lib().vd_gemm_tune_set(M, N, K, 1, 0, retired, 0) != 0
+            assert b"vd_gemm_tune_set" in lib().vd_last_error() and str(retired).encode() in lib().vd_last_error()
+            assert plan(M, N, K) == before
+        assert lib().vd_gemm_tune_set(M, N, K, 1, 0, T128x64, 4) == 0        # a built slot is still accepted
+        assert plan(M, N, K) == (T128x64, 4)
+        assert lib().vd_gemm_tune_set(M, N, K, 1, 0, T256x256, 0) != 0       # ... and a refused entry does not overwrite it
+        assert plan(M, N, K) == (T128x64, 4)
+    finally:
+        lib().vd_gemm_tune_clear()
+
+
+def test_plan_grid_matches_the_recorded_planner(tmp_path):
+    """tests/golden/gemm_plan_grid.npz holds what every planning entry point answered, over the grid of tools/gen_plan_grid.py,
+    in a build of the commit before the launch decisions moved into one table per kernel family.  The grid is replayed against the
+    current library (fresh child process, planner switches removed from the environment) and every recorded array compared for
+    equality: no case is skipped or filtered."""
+    import subprocess
+    import numpy as np
+    out = str(tmp_path / "replay.npz")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_plan_grid.py"), "--out", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    want = np.load(os.path.join(ROOT, "tests", "golden", "gemm_plan_grid.npz"))
+    got = np.load(out)
+    assert sorted(got.files) == sorted(want.files)
+    assert int(want["n_descriptors"][0]) > 400000 and want["plan"].shape == (3, int(want["n_descriptors"][0]))
+    for name in want.files:
+        w, g = want[name], got[name]
+        assert w.shape == g.shape and w.dtype == g.dtype, name
+        diff = np.argwhere(w != g)
+        assert len(diff) == 0, "%s: %d of %d entries differ, first at %s: recorded %s, now %s" % (
+            name, len(diff), w.size, diff[0].tolist(), w[tuple(diff[0])], g[tuple(diff[0])])

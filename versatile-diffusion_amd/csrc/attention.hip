@@ -894,17 +894,7 @@ template <int D>
 int launch_attn_wide(AttnArgs a, hipStream_t stream) {
     constexpr int LDS = 2 * (2 * 32 * D * 2) + 2 * (4 * 64 * 16 * 4);
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_wide_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            vd_set_error("vd_attention_f16: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&attn_wide_kernel<D>}, LDS, done, "vd_attention_f16")) return rc;
     a.nqb = (a.Nq + 31) / 32;
     hipLaunchKernelGGL(attn_wide_kernel<D>, dim3(a.nqb * a.BH), dim3(256), LDS, stream, a);
     return vd_check_launch("vd_attention_f16");

@@ -1,27 +1,45 @@
-// Launch planner and the two-waves-per-SIMD instances of conv3x3_halo_kernel (conv_halo_kernel.h); the one-wave-per-SIMD
-// instances live in conv_halo_big.hip.  Reached from vd_gemm_f16 (gemm.hip) for every 3x3 / stride 1 / pad 1 convolution
-// whose geometry the halo formulation accepts.
+// Launch planner and the table of built instances of conv3x3_halo_kernel (conv_halo_kernel.h).  Reached from vd_gemm_f16
+// (gemm.hip) for every 3x3 / stride 1 / pad 1 convolution whose geometry the halo formulation accepts.
 #include "conv_halo_kernel.h"
 
 namespace {
 
-struct HaloVariant { int bm, bn, nt, mode; const char* name; };
-// index = variant id (tile_cfg of vd_gemm_plan = vd_gemm_num_configs() + id)
-const HaloVariant kHalo[VD_CONV_HALO_VARIANTS] = {
-    {256, 160, 512, 0, "conv3x3_halo_kernel<256,160,32,160,512,0>"},
-    {256, 160, 512, 1, "conv3x3_halo_kernel<256,160,32,160,512,1>"},
-    {256, 160, 512, 2, "conv3x3_halo_kernel<256,160,32,160,512,2>"},
-    {256, 128, 512, 0, "conv3x3_halo_kernel<256,128,64,64,512,0>"},
-    {256, 128, 512, 1, "conv3x3_halo_kernel<256,128,64,64,512,1>"},
-    {256, 128, 512, 2, "conv3x3_halo_kernel<256,128,64,64,512,2>"},
-    {256, 160, 256, 1, "conv3x3_halo_kernel<256,160,64,160,256,1>"},
-    {256, 160, 256, 2, "conv3x3_halo_kernel<256,160,64,160,256,2>"},
-    {256, 160, 512, 3, "conv3x3_halo_kernel<256,160,32,160,512,3>"},
-    {256, 128, 512, 3, "conv3x3_halo_kernel<256,128,64,64,512,3>"},
-    {128, 32, 256, 4, "conv3x3_halo_kernel<128,32,32,32,256,4>"},
-    {128, 160, 256, 2, "conv3x3_halo_kernel<128,160,32,160,256,2>"},
-    {256, 160, 512, 2, "conv3x3_halo_kernel<256,160,32,160,512,2,skip>"},
+// ---- The built variants: one row each, and the only place a variant's template arguments are written. ----------------------
+//   X(slot, BM, BN, WM, WN, NT, MODE, skip)      skip: the instance with the folded 1x1 skip convolution
+#define VD_HALO_VARIANTS(X)                          \
+    X(HALO_PLANNER, 256, 160, 32, 160, 512, 2, false) \
+    X(HALO_VAE,     256, 128, 64,  64, 512, 2, false) \
+    X(HALO_SKIP,    256, 160, 32, 160, 512, 2, true)
+
+struct HaloVariant { int slot, bm, bn, nt, mode; bool skip; const char* name; };
+constexpr HaloVariant kHalo[] = {
+#define X(slot, BM, BN, WM, WN, NT, MODE, skip)              \
+    {slot, BM, BN, NT, MODE, skip,                           \
+     skip ? "conv3x3_halo_kernel<" #BM "," #BN "," #WM "," #WN "," #NT "," #MODE ",skip>" : "conv3x3_halo_kernel<" #BM "," #BN "," #WM "," #WN "," #NT "," #MODE ">"},
+    VD_HALO_VARIANTS(X)
+#undef X
 };
+// the row of a built slot, nullptr for everything else
+constexpr const HaloVariant* halo_of(int variant) {
+    for (const HaloVariant& h : kHalo)
+        if (h.slot == variant) return &h;
+    return nullptr;
+}
+// Retired slots: development variants (barrier placements 0 / 1 / 3, one wave per SIMD, whole-K small-M blocks, 128-pixel patches)
+// that lost their in-forward A/Bs (profiles/HISTORY.md); round 6 removed the instantiations.  They keep index and name (nullptr: a
+// built slot, named by the table above).
+constexpr const char* kRetiredHalo[VD_CONV_HALO_VARIANTS] = {
+    "conv3x3_halo_kernel<256,160,32,160,512,0>", "conv3x3_halo_kernel<256,160,32,160,512,1>", nullptr,
+    "conv3x3_halo_kernel<256,128,64,64,512,0>",  "conv3x3_halo_kernel<256,128,64,64,512,1>",  nullptr,
+    "conv3x3_halo_kernel<256,160,64,160,256,1>", "conv3x3_halo_kernel<256,160,64,160,256,2>", "conv3x3_halo_kernel<256,160,32,160,512,3>",
+    "conv3x3_halo_kernel<256,128,64,64,512,3>",  "conv3x3_halo_kernel<128,32,32,32,256,4>",   "conv3x3_halo_kernel<128,160,32,160,256,2>",
+    nullptr};
+constexpr bool halo_table_ok() {
+    for (int v = 0; v < VD_CONV_HALO_VARIANTS; ++v)   // every slot is either built or retired
+        if ((halo_of(v) != nullptr) == (kRetiredHalo[v] != nullptr)) return false;
+    return true;
+}
+static_assert(halo_table_ok(), "VD_HALO_VARIANTS / kRetiredHalo disagree");
 
 std::atomic<int> g_halo_variant{-2};   // -2: not read from the environment yet; -1: planner; 0: off; k > 0: force variant k - 1
 
@@ -30,7 +48,7 @@ int halo_setting() {
     if (v == -2) {
         const char* e = getenv("VD_CONV_HALO");
         v = e ? atoi(e) : -1;
-        if (v < -1 || v > VD_CONV_HALO_VARIANTS || (v > 0 && !(v - 1 == 2 || v - 1 == 5 || v - 1 == 12))) v = -1;
+        if (v < -1 || v > VD_CONV_HALO_VARIANTS || (v > 0 && halo_of(v - 1) == nullptr)) v = -1;
         g_halo_variant.store(v, std::memory_order_relaxed);
     }
     return v;
@@ -94,20 +112,17 @@ bool halo_geometry(const GemmArgs& a, int BM, ConvHaloArgs& c) {
 
 }  // namespace
 
-// Instantiated: variants 2 (256 x 160 blocks, pinned mid-barrier loop: every UNet width), 5 (256 x 128: the VAE widths) and 12 (2 with
-// the folded skip convolution).  The other table slots were development variants (barrier placements 0 / 1 / 3, one wave per SIMD,
-// whole-K small-M blocks, 128-pixel patches) that lost their in-forward A/Bs (profiles/HISTORY.md); removed in round 6.
-static bool halo_built(int variant) { return variant == 2 || variant == 5 || variant == 12; }
-
 extern "C" int vd_conv_halo_set_variant(int v) {
     VD_REQUIRE(v >= -1 && v <= VD_CONV_HALO_VARIANTS, "vd_conv_halo_set_variant: %d out of range", v);
-    VD_REQUIRE(v <= 0 || halo_built(v - 1), "vd_conv_halo_set_variant: variant %d is not instantiated", v - 1);
+    VD_REQUIRE(v <= 0 || halo_of(v - 1) != nullptr, "vd_conv_halo_set_variant: variant %d is not instantiated", v - 1);
     g_halo_variant.store(v, std::memory_order_relaxed);
     return VD_OK;
 }
 
 const char* vd_conv_halo_name(int variant) {
-    return (variant >= 0 && variant < VD_CONV_HALO_VARIANTS) ? kHalo[variant].name : nullptr;
+    if (variant < 0 || variant >= VD_CONV_HALO_VARIANTS) return nullptr;
+    const HaloVariant* h = halo_of(variant);
+    return h ? h->name : kRetiredHalo[variant];
 }
 
 // Decide whether (and how) the validated problem *gemm_args runs on the halo kernel.  Returns 1 and fills conv_args
@@ -126,11 +141,11 @@ int vd_conv_halo_plan(const void* gemm_args, int can_split, void* conv_args, int
         // UNet width (320 / 640 / 1280) -- although 64 x 64 wave tiles (256 x 128 blocks) are 5-15 % faster back to back with
         // warm weights (tools/halo_check.py time), they lose 0.2 ms per forward where weights stream cold; they serve the
         // widths 160 does not divide (the VAE's 128 / 256 / 512)
-        if (d.N % 160 == 0) v = 2;
-        else if (d.N % 128 == 0) v = 5;
+        if (d.N % 160 == 0) v = HALO_PLANNER;
+        else if (d.N % 128 == 0) v = HALO_VAE;
         else return 0;
     }
-    const HaloVariant& hv = kHalo[v];
+    const HaloVariant& hv = *halo_of(v);   // (a forced setting is a built variant: halo_setting, vd_conv_halo_set_variant)
     ConvHaloArgs& c = *static_cast<ConvHaloArgs*>(conv_args);
     if (!halo_geometry(a, hv.bm, c)) return 0;
     c.g.tiles_n = (d.N + hv.bn - 1) / hv.bn;
@@ -165,7 +180,7 @@ int vd_conv_halo_plan(const void* gemm_args, int can_split, void* conv_args, int
     c.skip_cps = 0;
     if (d.skip_a0 != nullptr && d.skip_w != nullptr) {
         // folded 1x1 skip convolution: the planner's 256 x 160 instance only, inputs on the output grid
-        if (v != 2 || d.ups != 0 || d.skip_c0 % 64 != 0 || d.skip_c1 % 64 != 0 || d.skip_c0 <= 0 || (d.skip_a1 == nullptr && d.skip_c1 != 0)) return 0;
+        if (v != HALO_PLANNER || d.ups != 0 || d.skip_c0 % 64 != 0 || d.skip_c1 % 64 != 0 || d.skip_c0 <= 0 || (d.skip_a1 == nullptr && d.skip_c1 != 0)) return 0;
         const size_t rows = (size_t)d.M;
         const size_t b0 = rows * (size_t)d.skip_lda0 * 2, b1 = d.skip_a1 ? rows * (size_t)d.skip_lda1 * 2 : 0, bw = (size_t)d.N * d.skip_ldw * 2;
         if (b0 >= (1ull << 31) || b1 >= (1ull << 31) || bw >= (1ull << 31)) return 0;
@@ -174,7 +189,7 @@ int vd_conv_halo_plan(const void* gemm_args, int can_split, void* conv_args, int
         c.s0_bytes = (unsigned)b0;
         c.s1_bytes = (unsigned)b1;
         c.sw_bytes = (unsigned)bw;
-        v = 12;
+        v = HALO_SKIP;
     }
     *variant_out = v;
     *nsplit_out = ns;
@@ -185,9 +200,10 @@ int vd_conv_halo_plan(const void* gemm_args, int can_split, void* conv_args, int
 int vd_conv_halo_launch(const void* conv_args, int variant, int nsplit, hipStream_t stream) {
     const ConvHaloArgs& c = *static_cast<const ConvHaloArgs*>(conv_args);
     switch (variant) {
-        case 2: return launch_conv_halo<256, 160, 32, 160, 512, 2>(c, nsplit, stream);
-        case 5: return launch_conv_halo<256, 128, 64, 64, 512, 2>(c, nsplit, stream);
-        case 12: return launch_conv_halo<256, 160, 32, 160, 512, 2, true>(c, nsplit, stream);
+#define X(slot, BM, BN, WM, WN, NT, MODE, skip) \
+    case slot: return launch_conv_halo<BM, BN, WM, WN, NT, MODE, skip>(c, nsplit, stream);
+        VD_HALO_VARIANTS(X)
+#undef X
         default:
             vd_set_error("conv3x3_halo: variant %d is not instantiated", variant);
             return VD_ERR_UNSUPPORTED;

@@ -1,6 +1,5 @@
 // Halo-resident 3x3 convolution (stride 1, pad 1, optional nearest-2x upsample in front, optional two-source channel
-// concat) as an MFMA implicit GEMM for gfx950.  Included by conv_halo.hip (two waves per SIMD) and conv_halo_big.hip
-// (one wave per SIMD).
+// concat) as an MFMA implicit GEMM for gfx950.  Included by conv_halo.hip (planner and the table of built instances).
 //
 //   out[pixel][n] = epilogue( sum_{tap, c} X[pixel + tap][c] * W[n][tap][c] )
 //
@@ -578,6 +577,13 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     VD_TL_FLUSH(p.g.tl);
 }
 
+// The built variants by slot (tile_cfg of vd_gemm_plan = vd_gemm_num_configs() + slot); their rows are in conv_halo.hip.
+enum HaloVariantId {
+    HALO_PLANNER = 2,   // 256 x 160 blocks, pinned mid-barrier loop: the planner's choice for every UNet width
+    HALO_VAE = 5,       // 256 x 128 blocks: the widths 160 does not divide (the VAE's 128 / 256 / 512)
+    HALO_SKIP = 12      // HALO_PLANNER with the folded 1x1 skip convolution
+};
+
 template <int BM, int BN, int WM, int WN, int NT, int MODE, bool SKIP = false>
 int launch_conv_halo(const ConvHaloArgs& a, int nsplit, hipStream_t stream) {
     constexpr int WST = 3;
@@ -589,18 +595,7 @@ int launch_conv_halo(const ConvHaloArgs& a, int nsplit, hipStream_t stream) {
         return VD_ERR_UNSUPPORTED;
     }
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            vd_set_error("conv3x3_halo: cannot reserve LDS: %s", hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP>}, 160 * 1024, done, "conv3x3_halo", -1)) return rc;
     dim3 grid(a.g.tiles_m * a.g.tiles_n, nsplit, 1);
     hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP>), grid, dim3(NT), lds, stream, a);
     return vd_check_launch("conv3x3_halo");

@@ -28,17 +28,7 @@ int launch_wstream(const WsArgs& w, int blocks, hipStream_t stream) {
     constexpr int LDS = 2 * 4 * (((IPB * WS_GPX * 128 + 1023) / 1024 + 3) / 4) * 1024;   // two halo buffers
     if constexpr (LDS > 64 * 1024) {
         static std::atomic<unsigned long long> done{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(done.load(std::memory_order_acquire) & bit)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wstream_kernel<D, OCC, IPB>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) {
-                vd_set_error("vd_conv3x3_wstream_f16: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(e));
-                return VD_ERR_LAUNCH;
-            }
-            done.fetch_or(bit, std::memory_order_release);
-        }
+        if (const int rc = vd_reserve_lds({(const void*)&conv3x3_wstream_kernel<D, OCC, IPB>}, LDS, done, "vd_conv3x3_wstream_f16")) return rc;
     }
     hipLaunchKernelGGL((conv3x3_wstream_kernel<D, OCC, IPB>), dim3(blocks), dim3(256), LDS, stream, w);
     return vd_check_launch("vd_conv3x3_wstream_f16");
@@ -174,21 +164,9 @@ extern "C" int vd_conv3x3_wstream_f16(const VdGemmDesc* dp, const void* w_stream
         k.w.nsplit = 1;
         k.w.skip_cps = 0;
         k.g = a;
-        {
-            k.rotate = 1;
-        }
+        k.rotate = 1;
         static std::atomic<unsigned long long> done{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(done.load(std::memory_order_acquire) & bit)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wsk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WK_LDS);
-            if (e != hipSuccess) {
-                vd_set_error("vd_conv3x3_wstream_f16: cannot reserve %d bytes of LDS: %s", WK_LDS, hipGetErrorString(e));
-                return VD_ERR_LAUNCH;
-            }
-            done.fetch_or(bit, std::memory_order_release);
-        }
+        if (const int rc = vd_reserve_lds({(const void*)&conv3x3_wsk_kernel}, WK_LDS, done, "vd_conv3x3_wstream_f16")) return rc;
         hipLaunchKernelGGL(conv3x3_wsk_kernel, dim3(k.w.tiles_m * (d.N / 32)), dim3(WK_NT), WK_LDS, stream, k);
         return vd_check_launch("vd_conv3x3_wstream_f16/whole-K");
     }

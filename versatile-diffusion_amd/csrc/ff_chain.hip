@@ -445,17 +445,7 @@ __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
 template <bool PRE, bool POST>
 int launch_ffc(const FCArgs& a, hipStream_t stream) {
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_chain_kernel<PRE, POST>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_LDS);
-        if (e != hipSuccess) {
-            vd_set_error("vd_ff_chain_f16: cannot reserve %d bytes of LDS: %s", FC_LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&ff_chain_kernel<PRE, POST>}, FC_LDS, done, "vd_ff_chain_f16")) return rc;
     hipLaunchKernelGGL((ff_chain_kernel<PRE, POST>), dim3((unsigned)((a.M + FC_BM - 1) / FC_BM)), dim3(512), FC_LDS, stream, a);
     return vd_check_launch("vd_ff_chain_f16");
 }

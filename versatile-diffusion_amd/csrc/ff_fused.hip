@@ -375,25 +375,12 @@ extern "C" int vd_ff_geglu_f16(const void* x, const void* w1_packed, const void*
     VD_REQUIRE((((size_t)x | (size_t)w1_packed | (size_t)w2 | (size_t)res | (size_t)y) & 15) == 0 && (((size_t)b1_packed | (size_t)b2) & 7) == 0,
                "vd_ff_geglu_f16: operands must be 16-byte aligned (biases 8)");
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
+    if (const int rc = vd_reserve_lds({(const void*)&ff_geglu_kernel<0>, (const void*)&ff_geglu_kernel<1>}, FF_LDS, done, "vd_ff_geglu_f16")) return rc;
 #ifdef VD_FF_ABLATIONS
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ff_geglu_kernel<0, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, FF_LDS);
+    static std::atomic<unsigned long long> abl_done{0};   // (a failure here is ignored: the ablation launch itself reports it)
+    (void)vd_reserve_lds({(const void*)&ff_geglu_kernel<0, 1>, (const void*)&ff_geglu_kernel<0, 2>, (const void*)&ff_geglu_kernel<0, 3>,
+                          (const void*)&ff_geglu_kernel<0, 4>, (const void*)&ff_geglu_kernel<0, 5>}, FF_LDS, abl_done, "vd_ff_geglu_f16");
 #endif
-        if (e != hipSuccess) {
-            vd_set_error("vd_ff_geglu_f16: cannot reserve %d bytes of LDS: %s", FF_LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
     FFArgs a;
     a.x = (const f16*)x; a.w1 = (const f16*)w1_packed; a.b1 = (const f16*)b1_packed; a.w2 = (const f16*)w2; a.b2 = (const f16*)b2;
     a.res = (const f16*)res; a.y = (f16*)y; a.M = (int)M; a.eps = ln_eps;

@@ -1,5 +1,5 @@
-// vd_gemm_f16: validation, launch planner, the two-waves-per-SIMD instances of the kernel template in
-// gemm_kernel.h and the split-K reduce kernel.  (One-wave-per-SIMD instances: gemm_big.hip.)
+// vd_gemm_f16: validation, launch planner, the table of built instances of the kernel template in gemm_kernel.h and the
+// split-K reduce kernels.
 #include "gemm_kernel.h"
 #include "conv_halo_kernel.h"
 #include <mutex>
@@ -192,13 +192,27 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const GemmArgs
     }
 }
 
-inline void launch_reduce_stats(const GemmArgs& a, int nsplit, hipStream_t stream) {
-    const VdGemmDesc& d = a.d;
-    // (128-column blocks -- 512-byte row pieces, twice the loads in flight -- measured SLOWER inside the forward, 10.98 vs 10.89 ms:
-    // half as many blocks)
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel<8>, dim3((d.N + 63) / 64, d.M / 64, 1), dim3(256), 0, stream, a, nsplit);
-}
 
+// Sum `nsplit` fp32 slabs of d.ws and run the fused epilogue (zb: batch entries = the grid's z extent); with d.out_stats also the
+// per-channel statistics in partials of 64 rows (plan_stat_rows: batch 1, fp16 output, whole 64-row blocks per image).
+// from_gemm: the launch is named after vd_gemm_f16 in the error text (the weight-streaming entry points use the bare kernel name).
+int launch_reduce(const GemmArgs& a, int nsplit, int zb, hipStream_t stream, bool from_gemm = true) {
+    const VdGemmDesc& d = a.d;
+    const char* what;
+    if (d.out_stats != nullptr) {
+        // (128-column blocks -- 512-byte row pieces, twice the loads in flight -- measured SLOWER inside the forward, 10.98 vs 10.89 ms:
+        // half as many blocks)
+        hipLaunchKernelGGL(splitk_reduce_stats_kernel<8>, dim3((d.N + 63) / 64, d.M / 64, 1), dim3(256), 0, stream, a, nsplit);
+        what = "vd_gemm_f16/splitk_reduce_stats";
+    } else {
+        const size_t total = (size_t)d.M * ((d.N + 7) / 8);
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, zb), dim3(256), 0, stream, a, nsplit);
+        what = "vd_gemm_f16/splitk_reduce";
+    }
+    return vd_check_launch(from_gemm ? what : what + sizeof("vd_gemm_f16/") - 1);
+}
 
 }  // namespace
 
@@ -212,47 +226,103 @@ extern "C" size_t vd_gemm_workspace_bytes(const VdGemmDesc* d) {
 }
 
 namespace {
-// Instantiation table.  w4b = 4 waves, ONE wave per SIMD (up to 512 registers), large per-wave tiles (gemm_big.hip).
+// ---- The built tiles: one row each, and the only place a tile's template arguments are written. ----------------------------
+//   X(name, slot, BM, BN, WM, WN, NT, STAGES, KB, OCC, slots, fold, geglu, rowsum)
+//   slot    tile_cfg of the C ABI (vd_gemm_plan, vd_gemm_tune_set, vd_gemm_set_override, configuration indices in profiles)
+//   OCC     blocks per CU the kernel is compiled for.  T128x128d asks for 1 where its neighbours ask for 2: its three stages take
+//           96 KiB of the CU's 160 KiB of LDS, so two of its blocks never share a CU.
+//   slots   co-resident blocks on the chip (LDS / VGPR limits per CU x 256 CUs) as the planner counts them: the round size of
+//           the cost model and what the split of a forced tile fills once (a "d" tile counts like its two-stage neighbour)
+//   fold    the slot whose LayerNorm-fold instance (a compile-time variant of the kernel) serves this tile: itself where one
+//           is built, else its two-stage neighbour
+//   geglu   a forced tile (override) may take a GEGLU launch: value / gate pairs need 128-column tiles
+//   rowsum  VdGemmDesc.row_sums applies: the fast write-out path with a power-of-two number of 16-byte segments per tile row
+//           (the two-pass epilogue of the 320-column tile keeps the plain path)
+// Suffixes: w8 = 8 waves (4 per SIMD); d = three stages ("deep" ring) for grids that do not fill the chip.
+#define VD_GEMM_TILES(X)                                                                        \
+    X(T128x128,    0, 128, 128, 64,  64, 256, 2, 64, 2,  512, T128x128,   true,  true)          \
+    X(T128x64,     1, 128,  64, 64,  32, 256, 2, 64, 2,  768, T128x64,    false, true)          \
+    X(T64x64,      2,  64,  64, 32,  32, 256, 2, 64, 2, 1024, T64x64,     false, true)          \
+    X(T128x128w8,  3, 128, 128, 32,  64, 512, 2, 64, 4,  256, T128x128w8, true,  true)          \
+    X(T128x64w8,   4, 128,  64, 32,  32, 512, 2, 64, 4,  256, T128x64w8,  false, true)          \
+    X(T128x320,    7, 128, 320, 32, 160, 512, 2, 64, 2,  256, T128x320,   false, false)         \
+    X(T128x128d,  13, 128, 128, 64,  64, 256, 3, 64, 1,  512, T128x128,   true,  true)          \
+    X(T128x64d,   14, 128,  64, 64,  32, 256, 3, 64, 2,  768, T128x64,    false, true)          \
+    X(T64x64d,    15,  64,  64, 32,  32, 256, 3, 64, 2, 1024, T64x64d,    false, true)
+
 enum TileCfg {
-    T128x128 = 0, T128x64 = 1, T64x64 = 2, T128x128w8 = 3, T128x64w8 = 4, T256x128 = 5, T128x256 = 6, T128x320 = 7,
-    T128x320b = 8, T128x256b = 9, T256x128b = 10, T128x160 = 11, T128x320b32 = 12, T128x128d = 13, T128x64d = 14, T64x64d = 15,
-    // 32-deep K tiles, 4-stage ring (same LDS footprint as 64-deep / 2 stages, tiles issued 3 ahead instead of 1)
-    T128x128q = 16, T128x64q = 17, T64x64q = 18, T128x128w8q = 19, T128x320q = 20, T128x160q = 21,
-    T256x320 = 22, T256x320q = 23, T256x256 = 24,
-    // 3 stages, mid-barrier main loop with pinned one-k-step-ahead fragment requests (gemm_kernel.h: MID)
-    T256x128m = 25, T128x128m = 26,
+#define X(name, slot, ...) name = slot,
+    VD_GEMM_TILES(X)
+#undef X
     T_COUNT = 27
 };
-struct CfgInfo { int bm, bn; const char* name; };
-const CfgInfo kCfg[T_COUNT] = {
-    {128, 128, "gemm_f16_kernel<128,128,64,64,256,2,64>"},   {128, 64, "gemm_f16_kernel<128,64,64,32,256,2,64>"},
-    {64, 64, "gemm_f16_kernel<64,64,32,32,256,2,64>"},       {128, 128, "gemm_f16_kernel<128,128,32,64,512,2,64>"},
-    {128, 64, "gemm_f16_kernel<128,64,32,32,512,2,64>"},     {256, 128, "gemm_f16_kernel<256,128,64,64,512,2,64>"},
-    {128, 256, "gemm_f16_kernel<128,256,64,64,512,2,64>"},   {128, 320, "gemm_f16_kernel<128,320,32,160,512,2,64>"},
-    {128, 320, "gemm_f16_kernel<128,320,64,160,256,2,64>"},  {128, 256, "gemm_f16_kernel<128,256,64,128,256,3,64>"},
-    {256, 128, "gemm_f16_kernel<256,128,128,64,256,3,64>"},  {128, 160, "gemm_f16_kernel<128,160,32,160,256,2,64>"},
-    {128, 320, "gemm_f16_kernel<128,320,64,160,256,4,32>"},  {128, 128, "gemm_f16_kernel<128,128,64,64,256,3,64>"},
-    {128, 64, "gemm_f16_kernel<128,64,64,32,256,3,64>"},     {64, 64, "gemm_f16_kernel<64,64,32,32,256,3,64>"},
-    {128, 128, "gemm_f16_kernel<128,128,64,64,256,4,32>"},   {128, 64, "gemm_f16_kernel<128,64,64,32,256,4,32>"},
-    {64, 64, "gemm_f16_kernel<64,64,32,32,256,4,32>"},       {128, 128, "gemm_f16_kernel<128,128,32,64,512,4,32>"},
-    {128, 320, "gemm_f16_kernel<128,320,32,160,512,4,32>"},  {128, 160, "gemm_f16_kernel<128,160,32,160,256,4,32>"},
-    {256, 320, "gemm_f16_kernel<256,320,64,160,512,2,64>"},  {256, 320, "gemm_f16_kernel<256,320,64,160,512,4,32>"},
-    {256, 256, "gemm_f16_kernel<256,256,64,128,512,2,64>"},
-    {256, 128, "gemm_f16_kernel<256,128,64,64,512,3,64>"},   {128, 128, "gemm_f16_kernel<128,128,32,64,512,3,64>"}};
+struct Tile { int slot, bm, bn, slots, fold; bool geglu, rowsum, emits_stats; const char* name; };
+constexpr Tile kTiles[] = {
+#define X(name, slot, BM, BN, WM, WN, NT, STAGES, KB, OCC, slots, fold, geglu, rowsum)                                        \
+    {slot, BM, BN, slots, fold, geglu, rowsum, gemm_emits_stats<BM, BN, NT, STAGES, KB, false>(),                              \
+     "gemm_f16_kernel<" #BM "," #BN "," #WM "," #WN "," #NT "," #STAGES "," #KB ">"},
+    VD_GEMM_TILES(X)
+#undef X
+};
+// the row of a built slot, nullptr for everything else
+constexpr const Tile* tile_of(int cfg) {
+    for (const Tile& t : kTiles)
+        if (t.slot == cfg) return &t;
+    return nullptr;
+}
 
-// Tiles that are instantiated.  Rounds 1-5 carried 18 more as development tiles (256x128, 128x256, 128x160, the one-wave-per-SIMD
+// Retired slots.  Rounds 1-5 carried 18 more tiles as development instances (256x128, 128x256, 128x160, the one-wave-per-SIMD
 // "b" tiles, the 32-deep / 4-stage "q" ring, 256x320, 256x256, the mid-barrier "m" loop): each lost its in-forward A/B at least
-// twice (profiles/HISTORY.md); round 6 removed the instantiations.  The table keeps their slots so configuration indices and
-// names in old profiles stay meaningful.
-bool cfg_built(int cfg) {
+// twice (profiles/HISTORY.md); round 6 removed the instantiations.  Their slots keep index and name, and nothing else, so
+// configuration indices and names in old profiles stay meaningful (nullptr: a built slot, named by the table above).
+constexpr const char* kRetiredName[T_COUNT] = {
+    nullptr, nullptr, nullptr, nullptr, nullptr,
+    "gemm_f16_kernel<256,128,64,64,512,2,64>",   "gemm_f16_kernel<128,256,64,64,512,2,64>",   nullptr,
+    "gemm_f16_kernel<128,320,64,160,256,2,64>",  "gemm_f16_kernel<128,256,64,128,256,3,64>",  "gemm_f16_kernel<256,128,128,64,256,3,64>",
+    "gemm_f16_kernel<128,160,32,160,256,2,64>",  "gemm_f16_kernel<128,320,64,160,256,4,32>",  nullptr, nullptr, nullptr,
+    "gemm_f16_kernel<128,128,64,64,256,4,32>",   "gemm_f16_kernel<128,64,64,32,256,4,32>",    "gemm_f16_kernel<64,64,32,32,256,4,32>",
+    "gemm_f16_kernel<128,128,32,64,512,4,32>",   "gemm_f16_kernel<128,320,32,160,512,4,32>",  "gemm_f16_kernel<128,160,32,160,256,4,32>",
+    "gemm_f16_kernel<256,320,64,160,512,2,64>",  "gemm_f16_kernel<256,320,64,160,512,4,32>",  "gemm_f16_kernel<256,256,64,128,512,2,64>",
+    "gemm_f16_kernel<256,128,64,64,512,3,64>",   "gemm_f16_kernel<128,128,32,64,512,3,64>"};
+
+constexpr bool table_ok() {
+    for (int s = 0; s < T_COUNT; ++s)   // every slot is either built or retired
+        if ((tile_of(s) != nullptr) == (kRetiredName[s] != nullptr)) return false;
+    for (const Tile& t : kTiles)        // a fold instance to go to; row sums need a power-of-two number of 16-byte segments per tile row
+        if (tile_of(t.fold) == nullptr || tile_of(t.fold)->fold != t.fold || (t.rowsum && (t.bn / 8 & (t.bn / 8 - 1)) != 0)) return false;
+    return true;
+}
+static_assert(table_ok(), "VD_GEMM_TILES / kRetiredName disagree");
+
+// The launch of one built tile; the LayerNorm-fold instance exists (is instantiated) only where the table says so.
+template <int BM, int BN, int WM, int WN, int NT, int STAGES, int KB, int OCC, bool HAS_FOLD>
+int launch_tile(const GemmArgs& a, int cfg, int nsplit, hipStream_t stream) {
+    if (!(a.d.flags & VD_EPI_LNFOLD)) return launch_cfg<BM, BN, WM, WN, NT, STAGES, KB, OCC>(a, nsplit, stream);
+    if constexpr (HAS_FOLD) {
+        return launch_cfg<BM, BN, WM, WN, NT, STAGES, KB, OCC, true>(a, nsplit, stream);
+    } else {
+        vd_set_error("vd_gemm_f16: tile configuration %d has no LayerNorm-fold instance", cfg);
+        return VD_ERR_UNSUPPORTED;
+    }
+}
+int launch_gemm(const GemmArgs& a, int cfg, int nsplit, hipStream_t stream) {
     switch (cfg) {
-        case T128x128: case T128x64: case T64x64: case T128x128w8: case T128x64w8: case T128x320: case T128x128d: case T128x64d: case T64x64d:
-            return true;
-        default: return false;
+#define X(name, slot, BM, BN, WM, WN, NT, STAGES, KB, OCC, slots, fold, geglu, rowsum) \
+    case name: return launch_tile<BM, BN, WM, WN, NT, STAGES, KB, OCC, fold == name>(a, cfg, nsplit, stream);
+        VD_GEMM_TILES(X)
+#undef X
+        default:
+            vd_set_error("vd_gemm_f16: tile configuration %d is not instantiated", cfg);
+            return VD_ERR_UNSUPPORTED;
     }
 }
 
 std::atomic<int> g_override{-1};
+// VD_GEMM_TILE=<n>: the developer override from the environment (vd_gemm_set_override wins), read once
+const char* tile_env() {
+    static const char* const e = getenv("VD_GEMM_TILE");
+    return e;
+}
 
 // Tuned launch table: (M, N, K, ksize, epilogue class) -> (tile configuration, split-K), filled by the host from a file
 // measured INSIDE a UNet forward (tools/tune_forward.py -> lib/gemm_tune.py); shapes that are not in it go through the
@@ -263,21 +333,17 @@ std::vector<TuneEntry> g_tune;
 inline int epi_class(const VdGemmDesc& d) {
     return (d.act == VD_ACT_GEGLU ? 1 : 0) | ((d.flags & VD_EPI_LNFOLD) ? 2 : 0) | (d.a1 ? 4 : 0);
 }
-
-// which gemm_f16_kernel instances (as launched below) can emit VdGemmDesc.out_stats from their epilogue
-bool cfg_emits_stats(int cfg) {
-    switch (cfg) {
-        case T128x128: return gemm_emits_stats<128, 128, 256, 2, 64, false>();
-        case T128x64: return gemm_emits_stats<128, 64, 256, 2, 64, false>();
-        case T64x64: return gemm_emits_stats<64, 64, 256, 2, 64, false>();
-        case T128x128w8: return gemm_emits_stats<128, 128, 512, 2, 64, false>();
-        case T128x64w8: return gemm_emits_stats<128, 64, 512, 2, 64, false>();
-        case T128x320: return gemm_emits_stats<128, 320, 512, 2, 64, false>();
-        case T128x128d: return gemm_emits_stats<128, 128, 256, 3, 64, false>();
-        case T128x64d: return gemm_emits_stats<128, 64, 256, 3, 64, false>();
-        case T64x64d: return gemm_emits_stats<64, 64, 256, 3, 64, false>();
-        default: return false;   // development tiles: the host falls back to vd_chan_stats_f16
-    }
+// the table's entry for the (normalised) problem, if there is one
+bool tuned_entry(const VdGemmDesc& d, TuneEntry& out) {
+    if (d.batch != 1) return false;
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    const int cls = epi_class(d);
+    for (const TuneEntry& t : g_tune)
+        if (t.M == d.M && t.N == d.N && t.K == d.K && t.ks == d.ksize && t.cls == cls) {
+            out = t;
+            return true;
+        }
+    return false;
 }
 
 // rows per statistics partial the planned launch writes to d.out_stats (0: it cannot)
@@ -298,13 +364,14 @@ int plan_stat_rows(const GemmArgs& a, int cfg, int nsplit, const ConvHaloArgs* h
         return (d.sync == nullptr && HW % 64 == 0) ? 64 : 0;
     }
     if (nsplit > 1) return (d.sync == nullptr && HW % 64 == 0) ? 64 : 0;   // splitk_reduce_stats_kernel
-    if (!cfg_emits_stats(cfg)) return 0;
-    const int bm = kCfg[cfg].bm;
+    const Tile* t = tile_of(cfg);
+    if (t == nullptr || !t->emits_stats) return 0;   // (an instance that cannot: the host falls back to vd_chan_stats_f16)
+    const int bm = t->bm;
     return HW % bm == 0 ? bm : (bm % HW == 0 ? HW : 0);
 }
 
-// validate + normalise the descriptor and pick tile shape / split factor
-int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, ConvHaloArgs* halo = nullptr) {
+// validate the descriptor, fill its defaults and the byte extents of the operands
+int normalise(const VdGemmDesc* dp, GemmArgs& a) {
     VD_REQUIRE(dp != nullptr, "vd_gemm_f16: null descriptor");
     a.d = *dp;
     VdGemmDesc& d = a.d;
@@ -359,8 +426,7 @@ int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, 
         VD_REQUIRE(d.act == VD_ACT_NONE && d.alpha == 1.0f, "vd_gemm_f16: rowvec epilogue requires act=none, alpha=1");
     if (d.flags & VD_EPI_OUT_F32)
         VD_REQUIRE(!(d.flags & (VD_EPI_ROWVEC | VD_EPI_RESIDUAL)) && d.act != VD_ACT_GEGLU, "vd_gemm_f16: fp32 output supports bias/act/alpha only");
-    const bool lnfold = (d.flags & VD_EPI_LNFOLD) != 0;
-    if (lnfold) {
+    if (d.flags & VD_EPI_LNFOLD) {
         VD_REQUIRE(d.colsum != nullptr, "vd_gemm_f16: LayerNorm fold needs colsum");
         // statistics inside the K loop (one-pass E[x^2] - mean^2 on the raw fp16 operands, less robust than the two-pass
         // vd_row_stats_f16) only on explicit request: a forgotten ln_stats pointer is an error, not a silent downgrade
@@ -373,77 +439,53 @@ int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, 
     }
 
     a.kt_total = (d.K + BK - 1) / BK;
-    {
-        const size_t in_rows = (size_t)(d.M / (d.Hout * d.Wout)) * d.Hin * d.Win;
-        const size_t a0b = in_rows * (size_t)d.lda0 * 2, a1b = d.a1 ? in_rows * (size_t)d.lda1 * 2 : 0;
-        const size_t wb = (size_t)d.N * d.ldw * 2;
-        VD_REQUIRE(a0b < (1ull << 31) && a1b < (1ull << 31) && wb < (1ull << 31),
-                   "vd_gemm_f16: operand larger than 2 GiB per batch entry (32-bit buffer offsets); split the batch");
-        a.a0_bytes = (unsigned)a0b;
-        a.a1_bytes = (unsigned)a1b;
-        a.w_bytes = (unsigned)wb;
-        a.plain = (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.ups == 0 && d.Hin * d.Win == d.Hout * d.Wout) ? 1 : 0;
-    }
+    const size_t in_rows = (size_t)(d.M / (d.Hout * d.Wout)) * d.Hin * d.Win;
+    const size_t a0b = in_rows * (size_t)d.lda0 * 2, a1b = d.a1 ? in_rows * (size_t)d.lda1 * 2 : 0;
+    const size_t wb = (size_t)d.N * d.ldw * 2;
+    VD_REQUIRE(a0b < (1ull << 31) && a1b < (1ull << 31) && wb < (1ull << 31),
+               "vd_gemm_f16: operand larger than 2 GiB per batch entry (32-bit buffer offsets); split the batch");
+    a.a0_bytes = (unsigned)a0b;
+    a.a1_bytes = (unsigned)a1b;
+    a.w_bytes = (unsigned)wb;
+    a.plain = (d.ksize == 1 && d.stride == 1 && d.pad == 0 && d.ups == 0 && d.Hin * d.Win == d.Hout * d.Wout) ? 1 : 0;
+    return VD_OK;
+}
 
-    // ---- tile / split choice: a small cost model, calibrated on MI355X with tools/gemm_sweep.py.
-    // A launch runs in "rounds" of `cap` co-resident blocks (LDS / VGPR limits per CU x 256 CUs); the time of one
-    // 64-deep K tile of one block depends on how full the CUs are (t_solo: <= 1 block per CU .. t_full: every slot
-    // taken; the chip also clocks higher when part of it idles).  Split-K adds the fp32 slab round trip + one reduce
-    // launch.  What this buys over fixed thresholds: grids that just overflow a round (e.g. 640 blocks on 512 slots
-    // ran 2 rounds at 25 % more time than 480 blocks in one) are avoided.
-    struct Cand { TileCfg cfg; int cap; float t_solo, t_full, lo, hi, fix; bool split_ok; };
-    static const Cand cands[] = {
-        {T128x128, 512, 0.75f, 1.10f, 0.50f, 1.00f, 6.5f, true},
-        {T128x64, 768, 0.50f, 1.00f, 0.25f, 0.83f, 4.f, true},
-        {T64x64, 1024, 0.38f, 0.78f, 0.25f, 0.75f, 3.f, true},
-        {T128x320, 256, 1.20f, 1.50f, 0.50f, 1.00f, 6.f, false}};
+// ---- tile / split choice for gemm_f16_kernel: a small cost model, calibrated on MI355X with tools/gemm_sweep.py.
+// A launch runs in "rounds" of `slots` co-resident blocks (the table above); the time of one 64-deep K tile of one block depends
+// on how full the CUs are (t_solo: <= 1 block per CU .. t_full: every slot taken; the chip also clocks higher when part of it
+// idles).  Split-K adds the fp32 slab round trip + one reduce launch.  What this buys over fixed thresholds: grids that just
+// overflow a round (e.g. 640 blocks on 512 slots ran 2 rounds at 25 % more time than 480 blocks in one) are avoided.
+// Then, in this order: the tuned entry (te, or nullptr), the developer override, the deep ring for small grids, the 8-wave tile
+// for the LayerNorm-folded q|k|v of the 32x32 level, and the fold instance of the chosen tile.
+void choose_tile(const GemmArgs& a, bool can_split, const TuneEntry* te, TileCfg& cfg, int& nsplit) {
+    const VdGemmDesc& d = a.d;
+    struct Cand { const Tile* t; float t_solo, t_full, lo, hi, fix; bool split_ok; };
+    static constexpr Cand cands[] = {
+        {tile_of(T128x128), 0.75f, 1.10f, 0.50f, 1.00f, 6.5f, true},
+        {tile_of(T128x64), 0.50f, 1.00f, 0.25f, 0.83f, 4.f, true},
+        {tile_of(T64x64), 0.38f, 0.78f, 0.25f, 0.75f, 3.f, true},
+        {tile_of(T128x320), 1.20f, 1.50f, 0.50f, 1.00f, 6.f, false}};
     const int zb = d.batch;
-    const bool can_split = (d.ws != nullptr || d.split_k > 1) && d.act != VD_ACT_GEGLU && !(d.flags & VD_EPI_OUT_F32) && !lnfold;
+    const bool lnfold = (d.flags & VD_EPI_LNFOLD) != 0;
+    const int override_set = g_override.load(std::memory_order_relaxed);
+    auto tiles_of = [&](const Tile& t) { return ((d.M + t.bm - 1) / t.bm) * ((d.N + t.bn - 1) / t.bn) * zb; };
     auto model_us = [&](const Cand& c, int ns) {
-        const int bm = kCfg[c.cfg].bm, bn = kCfg[c.cfg].bn;
-        const int tiles = ((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn) * zb;
-        const long blocks = (long)tiles * ns;
+        const int cap = c.t->slots;
+        const long blocks = (long)tiles_of(*c.t) * ns;
         const int kt = (a.kt_total + ns - 1) / ns;
-        const long full = blocks / c.cap, rem = blocks % c.cap;
+        const long full = blocks / cap, rem = blocks % cap;
         float t = (float)full * (kt * c.t_full + c.fix);
         if (rem) {
-            const float load = (float)rem / c.cap;
+            const float load = (float)rem / cap;
             const float f = load <= c.lo ? 0.f : (load >= c.hi ? 1.f : (load - c.lo) / (c.hi - c.lo));
             t += kt * (c.t_solo + f * (c.t_full - c.t_solo)) + c.fix;
         }
         if (ns > 1) t += 3.f + 2.f * ns * (float)d.M * d.N * zb * 4.f / 8.0e6f + 2.f;  // slabs at ~8 TB/s (cache resident) + launch
         return t;
     };
-    // 3x3 convolutions on patch-shaped output grids: the halo-resident kernel (conv_halo.hip), unless a GEMM tile is forced
-    static const bool tile_env = getenv("VD_GEMM_TILE") != nullptr;
-    bool tuned_gemm_tile = false;   // a tuned-table entry for this 3x3 problem pins a gemm_f16_kernel tile: it vetoes the halo path
-    if (d.ksize == 3) {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        const int cls = epi_class(d);
-        for (const TuneEntry& t : g_tune)
-            if (t.M == d.M && t.N == d.N && t.K == d.K && t.ks == 3 && t.cls == cls && d.batch == 1) { tuned_gemm_tile = true; break; }
-    }
-    if (d.ksize == 3 && g_override.load(std::memory_order_relaxed) < 0 && !tile_env && !tuned_gemm_tile) {
-        ConvHaloArgs local;
-        ConvHaloArgs* h = halo ? halo : &local;
-        int hv = 0, hns = 1;
-        if (vd_conv_halo_plan(&a, can_split ? 1 : 0, h, &hv, &hns)) {
-            if (hns > 1) {
-                VD_REQUIRE(d.ws != nullptr, "vd_gemm_f16: split_k=%d needs a workspace", hns);
-                VD_REQUIRE(hns <= VD_MAX_SPLIT_K, "vd_gemm_f16: split_k=%d > %d", hns, VD_MAX_SPLIT_K);
-            }
-            a.tiles_m = h->g.tiles_m;
-            a.tiles_n = h->g.tiles_n;
-            a.kt_per_split = a.kt_total;
-            cfg_out = T_COUNT + hv;
-            nsplit_out = hns;
-            a.stat_rows = h->g.stat_rows = plan_stat_rows(a, cfg_out, hns, h);
-            return VD_OK;
-        }
-    }
-    VD_REQUIRE(d.skip_a0 == nullptr, "vd_gemm_f16: the folded skip convolution is taken by the halo-resident 3x3 convolution only (vd_gemm_skip_ok)");
-    TileCfg cfg = T64x64;
-    int nsplit = 1;
+    cfg = T64x64;
+    nsplit = 1;
     if (d.act == VD_ACT_GEGLU) {
         // 8 waves: the erf-heavy epilogue of one wave overlaps MFMAs of others.  (The 256x256 tile, 64x128 per wave, is
         // 1 % slower over the forward for the M >= 4096 GEGLU projections: 13.48 vs 13.36 ms, same box.)
@@ -476,43 +518,31 @@ int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, 
             for (int ns = (d.split_k > 0 ? d.split_k : 1); ns <= ns_max; ++ns) {
                 if (ns > 1 && (a.kt_total / ns < 8 || !c.split_ok)) break;
                 const float t = model_us(c, ns);
-                if (t < best) { best = t; cfg = c.cfg; nsplit = ns; }
+                if (t < best) { best = t; cfg = (TileCfg)c.t->slot; nsplit = ns; }
             }
         // the same N = 640 rows with a deep K (FF-out of the 32x32 level, K = 2560): 8 waves on the 128x128 tile, 0.02-0.04 ms
         // per forward over the 4-wave one (tools/tune_graph.py, two sessions)
         if (cfg == T128x128 && nsplit == 1 && d.ksize <= 1 && d.N > 320 && d.N <= 640 && d.M >= 8192) cfg = T128x128w8;
     }
+    // the tuned entry -- also with a caller-fixed split (ops.gemm plans first, then launches with split_k = the planned factor):
+    // the tuned tile is honoured when its split factor is the one requested
     bool tuned = false;
-    {   // also with a caller-fixed split (ops.gemm plans first, then launches with split_k = the planned factor): the tuned
-        // tile is honoured when its split factor is the one requested
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        const int cls = epi_class(d);
-        for (const TuneEntry& t : g_tune)
-            if (t.M == d.M && t.N == d.N && t.K == d.K && t.ks == d.ksize && t.cls == cls && d.batch == 1) {
-                if (d.split_k > 0 && (t.nsplit > 0 ? t.nsplit : 1) != d.split_k) break;
-                if (t.nsplit > 1 && !can_split) break;
-                if (d.act == VD_ACT_GEGLU && kCfg[t.cfg].bn % 128 != 0) break;
-                cfg = (TileCfg)t.cfg;
-                nsplit = t.nsplit > 0 ? t.nsplit : 1;
-                tuned = true;
-                break;
-            }
+    if (te != nullptr && !(d.split_k > 0 && (te->nsplit > 0 ? te->nsplit : 1) != d.split_k) && !(te->nsplit > 1 && !can_split) &&
+        !(d.act == VD_ACT_GEGLU && tile_of(te->cfg)->bn % 128 != 0)) {
+        cfg = (TileCfg)te->cfg;
+        nsplit = te->nsplit > 0 ? te->nsplit : 1;
+        tuned = true;
     }
     {   // developer override (vd_gemm_set_override / VD_GEMM_TILE=<n>): never set in production runs
-        static const char* ov_env = getenv("VD_GEMM_TILE");
-        int ov = g_override.load(std::memory_order_relaxed);
-        if (ov < 0 && ov_env) ov = atoi(ov_env);
-        const bool geglu_ok = ov == T128x128 || ov == T128x128w8 || ov == T128x128d;
-        if (ov >= 0 && ov < T_COUNT && cfg_built(ov) && (d.act != VD_ACT_GEGLU || geglu_ok) && !(d.M < 96 || d.N < 96)) {
+        int ov = override_set;
+        if (ov < 0 && tile_env()) ov = atoi(tile_env());
+        const Tile* forced = tile_of(ov);
+        if (forced != nullptr && (d.act != VD_ACT_GEGLU || forced->geglu) && !(d.M < 96 || d.N < 96)) {
             cfg = (TileCfg)ov;
             // re-plan the split for the forced tile: fill the chip once (one block per CU for the 1-block-per-CU tiles)
             nsplit = 1;
             if (d.split_k <= 0 && can_split && a.kt_total >= 32) {
-                const int tiles = ((d.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((d.N + kCfg[cfg].bn - 1) / kCfg[cfg].bn) * zb;
-                const int slots = (cfg == T128x128 || cfg == T128x128d) ? 512
-                                  : (cfg == T128x64 || cfg == T128x64d) ? 768
-                                  : (cfg == T64x64 || cfg == T64x64d) ? 1024 : 256;
-                nsplit = slots / tiles;
+                nsplit = forced->slots / tiles_of(*forced);
                 if (nsplit < 1) nsplit = 1;
                 if (nsplit > VD_MAX_SPLIT_K / 2) nsplit = VD_MAX_SPLIT_K / 2;
                 while (nsplit > 1 && a.kt_total / nsplit < 8) --nsplit;
@@ -521,14 +551,14 @@ int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, 
     }
     if (d.split_k > 0) nsplit = d.split_k;
     if (nsplit > a.kt_total) nsplit = a.kt_total;
-    if (g_override.load(std::memory_order_relaxed) < 0 && !tuned) {
+    if (override_set < 0 && !tuned) {
         const int ktps = (a.kt_total + nsplit - 1) / nsplit;
         // grids that cannot fill the CUs twice over are latency-bound per block: those get a deeper ring of 64-deep tiles
         // (round 4, tools/probes/gemm_timeline.py: raising the limit to "every block still co-resident" -- 768 blocks of 64x64,
         // 512 of 128x64 -- shortens the K loop of the M = 2048, N = K = 1280 projections from 11.6 to 10.1 us per block, not to
         // half: at 640 blocks x 16 KiB per k-step the loop runs at the L2 -> LDS fill rate, not at one round trip per k-step.
         // Forward unchanged (10.57 vs 10.57 ms), so the limit stays; VD_GEMM_DEEP_MAX moves it.)
-        const long grid_blocks = (long)((d.M + kCfg[cfg].bm - 1) / kCfg[cfg].bm) * ((d.N + kCfg[cfg].bn - 1) / kCfg[cfg].bn) * nsplit * zb;
+        const long grid_blocks = (long)tiles_of(*tile_of(cfg)) * nsplit;
         const long deep64 = 400, deep128 = 400;
         if (ktps >= 8) {
             if (cfg == T128x64 && grid_blocks <= deep128) cfg = T128x64d;
@@ -543,21 +573,47 @@ int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, 
     }
     // LayerNorm-folded q|k|v of the 32x32 level (K = 640, N = 1920): the 128x128 tile on 8 waves, 0.015 (t2i) .. 0.05 ms (i2v) per
     // forward over the 4-wave one in all four workloads (tools/tune_graph.py)
-    if (lnfold && !tuned && g_override.load(std::memory_order_relaxed) < 0 && (cfg == T128x128 || cfg == T128x320) && nsplit == 1 && a.kt_total > 5 && a.kt_total <= 10 && d.M >= 4096 &&
+    if (lnfold && !tuned && override_set < 0 && (cfg == T128x128 || cfg == T128x320) && nsplit == 1 && a.kt_total > 5 && a.kt_total <= 10 && d.M >= 4096 &&
         d.act != VD_ACT_GEGLU)
         cfg = T128x128w8;
-    if (lnfold) {
-        // the LayerNorm fold is a compile-time variant of the kernel, instantiated for these tiles only
-        switch (cfg) {
-            case T128x128: case T128x64: case T64x64: case T128x128w8: case T128x64w8: case T128x320: case T64x64d: break;
-            case T128x64d: cfg = T128x64; break;
-            case T128x128d: cfg = T128x128; break;
-            default: cfg = (d.act == VD_ACT_GEGLU) ? T128x128w8 : T128x128; break;
+    if (lnfold) cfg = (TileCfg)tile_of(cfg)->fold;   // every path above ends on a built tile
+}
+
+// validate + normalise the descriptor and pick kernel, tile shape and split factor
+int plan_gemm(const VdGemmDesc* dp, GemmArgs& a, int& cfg_out, int& nsplit_out, ConvHaloArgs* halo = nullptr) {
+    if (const int rc = normalise(dp, a)) return rc;
+    VdGemmDesc& d = a.d;
+    const bool lnfold = (d.flags & VD_EPI_LNFOLD) != 0;
+    const bool can_split = (d.ws != nullptr || d.split_k > 1) && d.act != VD_ACT_GEGLU && !(d.flags & VD_EPI_OUT_F32) && !lnfold;
+    TuneEntry te;
+    const bool has_te = tuned_entry(d, te);
+    // 3x3 convolutions on patch-shaped output grids: the halo-resident kernel (conv_halo.hip), unless a GEMM tile is forced or a
+    // tuned-table entry for the problem pins a gemm_f16_kernel tile
+    if (d.ksize == 3 && g_override.load(std::memory_order_relaxed) < 0 && !tile_env() && !has_te) {
+        ConvHaloArgs local;
+        ConvHaloArgs* h = halo ? halo : &local;
+        int hv = 0, hns = 1;
+        if (vd_conv_halo_plan(&a, can_split ? 1 : 0, h, &hv, &hns)) {
+            if (hns > 1) {
+                VD_REQUIRE(d.ws != nullptr, "vd_gemm_f16: split_k=%d needs a workspace", hns);
+                VD_REQUIRE(hns <= VD_MAX_SPLIT_K, "vd_gemm_f16: split_k=%d > %d", hns, VD_MAX_SPLIT_K);
+            }
+            a.tiles_m = h->g.tiles_m;
+            a.tiles_n = h->g.tiles_n;
+            a.kt_per_split = a.kt_total;
+            cfg_out = T_COUNT + hv;
+            nsplit_out = hns;
+            a.stat_rows = h->g.stat_rows = plan_stat_rows(a, cfg_out, hns, h);
+            return VD_OK;
         }
     }
-    const int bm = kCfg[cfg].bm, bn = kCfg[cfg].bn;
-    a.tiles_m = (d.M + bm - 1) / bm;
-    a.tiles_n = (d.N + bn - 1) / bn;
+    VD_REQUIRE(d.skip_a0 == nullptr, "vd_gemm_f16: the folded skip convolution is taken by the halo-resident 3x3 convolution only (vd_gemm_skip_ok)");
+    TileCfg cfg;
+    int nsplit;
+    choose_tile(a, can_split, has_te ? &te : nullptr, cfg, nsplit);
+    const Tile& t = *tile_of(cfg);
+    a.tiles_m = (d.M + t.bm - 1) / t.bm;
+    a.tiles_n = (d.N + t.bn - 1) / t.bn;
     if (nsplit > a.kt_total) nsplit = a.kt_total;
     if (nsplit > 1) {
         VD_REQUIRE(d.ws != nullptr, "vd_gemm_f16: split_k=%d needs a workspace", nsplit);
@@ -591,23 +647,19 @@ extern "C" int vd_gemm_skip_ok(const VdGemmDesc* dp) {
     ConvHaloArgs halo;
     int c = 0, n = 1;
     if (plan_gemm(dp, a, c, n, &halo) != VD_OK) return 0;
-    return c == T_COUNT + 12 ? 1 : 0;
+    return c == T_COUNT + HALO_SKIP ? 1 : 0;
 }
 
 // launches whose part 2 can accumulate VdGemmDesc.row_sums: an unsplit gemm_f16_kernel (not the halo conv, not a reduce kernel)
-// with the fast write-out path (vector-aligned fp16 output, residual OR row vector) and a power-of-two number of 16-byte
-// segments per tile row
+// with the fast write-out path (vector-aligned fp16 output, residual OR row vector) on a tile the table admits
 static bool row_sums_ok(const GemmArgs& a, int cfg, int nsplit) {
     const VdGemmDesc& d = a.d;
-    if (cfg >= T_COUNT || nsplit > 1 || d.act == VD_ACT_GEGLU) return false;
+    if (nsplit > 1 || d.act == VD_ACT_GEGLU) return false;
     if (d.flags & (VD_EPI_OUT_F32 | VD_EPI_BIAS_ALONG_M)) return false;
     if ((d.flags & VD_EPI_RESIDUAL) && (d.flags & VD_EPI_ROWVEC)) return false;
     if ((d.N & 7) || (d.ldc & 7) || (d.ldr & 7)) return false;
-    const int ch = kCfg[cfg].bn / 8;
-    if ((ch & (ch - 1)) != 0 || ch > 64) return false;
-    // two-pass epilogues (256 x 320) and the one-wave-per-SIMD development tiles keep the plain path
-    return cfg == T128x128 || cfg == T128x64 || cfg == T64x64 || cfg == T128x128w8 || cfg == T128x64w8 || cfg == T128x128d ||
-           cfg == T128x64d || cfg == T64x64d || cfg == T128x256 || cfg == T256x128;
+    const Tile* t = tile_of(cfg);
+    return t != nullptr && t->rowsum;
 }
 
 extern "C" int vd_gemm_row_sums_ok(const VdGemmDesc* dp) {
@@ -630,11 +682,15 @@ extern "C" int vd_gemm_plan(const VdGemmDesc* dp, int* tile_cfg, int* nsplit) {
 
 extern "C" const char* vd_gemm_config_name(int tile_cfg) {
     if (tile_cfg >= T_COUNT) return vd_conv_halo_name(tile_cfg - T_COUNT);
-    return (tile_cfg >= 0 && tile_cfg < T_COUNT) ? kCfg[tile_cfg].name : nullptr;
+    if (tile_cfg < 0) return nullptr;
+    const Tile* t = tile_of(tile_cfg);
+    return t ? t->name : kRetiredName[tile_cfg];
 }
 extern "C" int vd_gemm_num_configs(void) { return T_COUNT; }
 extern "C" int vd_gemm_tune_set(int M, int N, int K, int ksize, int epi_cls, int tile_cfg, int nsplit) {
     VD_REQUIRE(tile_cfg >= 0 && tile_cfg < T_COUNT && nsplit >= 0 && nsplit <= VD_MAX_SPLIT_K, "vd_gemm_tune_set: bad entry");
+    // (an entry for a retired slot would fail inside the forward; tools skip entries this call refuses)
+    VD_REQUIRE(tile_of(tile_cfg) != nullptr, "vd_gemm_tune_set: tile configuration %d is not instantiated", tile_cfg);
     std::lock_guard<std::mutex> lk(g_tune_mu);
     for (TuneEntry& t : g_tune)
         if (t.M == M && t.N == N && t.K == K && t.ks == (ksize > 0 ? ksize : 1) && t.cls == epi_cls) {
@@ -651,7 +707,7 @@ extern "C" int vd_gemm_tune_clear(void) {
     return VD_OK;
 }
 extern "C" int vd_gemm_set_override(int tile_cfg) {
-    if (tile_cfg >= 0 && !cfg_built(tile_cfg)) {
+    if (tile_cfg >= 0 && tile_of(tile_cfg) == nullptr) {
         vd_set_error("vd_gemm_set_override: tile configuration %d is not instantiated", tile_cfg);
         return VD_ERR_UNSUPPORTED;
     }
@@ -703,92 +759,32 @@ extern "C" int vd_gemm_f16(const VdGemmDesc* dp, hipStream_t stream) {
         a.mfast = (zb == 1 && mfast < 0.8 * nfast) ? 1 : 0;
         halo.g.mfast = a.mfast;
     }
-    if (cfg >= T_COUNT) {   // halo-resident 3x3 convolution; split-K slabs go through the same reduce kernel
+    if (cfg >= T_COUNT) {   // halo-resident 3x3 convolution (batch 1); split-K slabs go through the same reduce kernel
         halo.g.nt_store = a.nt_store;
         // (the channel-chunk split is reduced by the reduce launch: the ticketed in-kernel reduction of rounds 4-5 -- VD_HALO_FIXUP,
         // with or without the XCD-local exchange -- measured equal at a 2-way split and 9 us slower per conv at 4-way; removed in round 6)
         halo.g.d.sync = nullptr;
         halo.g.xcd_local = 0;
         rc = vd_conv_halo_launch(&halo, cfg - T_COUNT, nsplit, stream);
-        if (rc != VD_OK) return rc;
-        if (nsplit > 1 && halo.g.d.sync == nullptr) {   // no ticket counters: slabs + the reduce kernel
-            a.d.sync = nullptr;
-            if (d.out_stats != nullptr) {
-                launch_reduce_stats(a, nsplit, stream);
-                return vd_check_launch("vd_gemm_f16/splitk_reduce_stats");
-            }
-            const size_t total = (size_t)d.M * ((d.N + 7) / 8);
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, 1), dim3(256), 0, stream, a, nsplit);
-            return vd_check_launch("vd_gemm_f16/splitk_reduce");
-        }
-        return VD_OK;
-    }
-    if ((long)a.tiles_m * a.tiles_n * zb > VD_GEMM_SYNC_INTS) a.d.sync = nullptr;  // more tiles than counters: two-kernel path
-    if (d.flags & VD_EPI_LNFOLD) {
-        switch (cfg) {
-            case T128x128: rc = launch_cfg<128, 128, 64, 64, 256, 2, 64, 2, true>(a, nsplit, stream); break;
-            case T128x64: rc = launch_cfg<128, 64, 64, 32, 256, 2, 64, 2, true>(a, nsplit, stream); break;
-            case T64x64: rc = launch_cfg<64, 64, 32, 32, 256, 2, 64, 2, true>(a, nsplit, stream); break;
-            case T64x64d: rc = launch_cfg<64, 64, 32, 32, 256, 3, 64, 2, true>(a, nsplit, stream); break;
-            case T128x128w8: rc = launch_cfg<128, 128, 32, 64, 512, 2, 64, 4, true>(a, nsplit, stream); break;
-            case T128x64w8: rc = launch_cfg<128, 64, 32, 32, 512, 2, 64, 4, true>(a, nsplit, stream); break;
-            case T128x320: rc = launch_cfg<128, 320, 32, 160, 512, 2, 64, 2, true>(a, nsplit, stream); break;
-            default:
-                vd_set_error("vd_gemm_f16: tile configuration %d has no LayerNorm-fold instance", cfg);
-                return VD_ERR_UNSUPPORTED;
-        }
-        return rc;
-    }
-    switch (cfg) {
-        case T128x128: rc = launch_cfg<128, 128, 64, 64, 256, 2, 64, 2>(a, nsplit, stream); break;
-        case T128x64: rc = launch_cfg<128, 64, 64, 32, 256, 2, 64, 2>(a, nsplit, stream); break;
-        case T64x64: rc = launch_cfg<64, 64, 32, 32, 256, 2, 64, 2>(a, nsplit, stream); break;
-        case T128x128w8: rc = launch_cfg<128, 128, 32, 64, 512, 2, 64, 4>(a, nsplit, stream); break;
-        case T128x64w8: rc = launch_cfg<128, 64, 32, 32, 512, 2, 64, 4>(a, nsplit, stream); break;
-        case T128x320: rc = launch_cfg<128, 320, 32, 160, 512, 2, 64, 2>(a, nsplit, stream); break;
-        case T128x128d: rc = launch_cfg<128, 128, 64, 64, 256, 3, 64, 1>(a, nsplit, stream); break;
-        case T128x64d: rc = launch_cfg<128, 64, 64, 32, 256, 3, 64, 2>(a, nsplit, stream); break;
-        case T64x64d: rc = launch_cfg<64, 64, 32, 32, 256, 3, 64, 2>(a, nsplit, stream); break;
-        default:
-            vd_set_error("vd_gemm_f16: tile configuration %d is not instantiated", cfg);
-            return VD_ERR_UNSUPPORTED;
+        a.d.sync = nullptr;   // no ticket counters: slabs + the reduce kernel
+    } else {
+        if ((long)a.tiles_m * a.tiles_n * zb > VD_GEMM_SYNC_INTS) a.d.sync = nullptr;  // more tiles than counters: two-kernel path
+        rc = launch_gemm(a, cfg, nsplit, stream);
     }
     if (rc != VD_OK) return rc;
-    if (nsplit > 1 && a.d.sync == nullptr) {
-        if (d.out_stats != nullptr) {   // plan_stat_rows: batch 1, fp16 output, whole 64-row blocks per image
-            launch_reduce_stats(a, nsplit, stream);
-            return vd_check_launch("vd_gemm_f16/splitk_reduce_stats");
-        }
-        const size_t total = (size_t)d.M * ((d.N + 7) / 8);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, zb), dim3(256), 0, stream, a, nsplit);
-        return vd_check_launch("vd_gemm_f16/splitk_reduce");
-    }
-    return VD_OK;
+    return (nsplit > 1 && a.d.sync == nullptr) ? launch_reduce(a, nsplit, zb, stream) : VD_OK;
 }
 
 
 // ---- helpers for conv_wstream.hip (its own translation unit: other compiler flags) ---------------------------------------
-// validate + normalise `desc` exactly as vd_gemm_f16 does; gemm_args_out: a GemmArgs
+// Validate + normalise `desc` exactly as vd_gemm_f16 does; gemm_args_out: a GemmArgs.  This runs the WHOLE planner, not only
+// its validation: what the planner rejects for the descriptor (a split without a workspace, ...) is part of what
+// vd_conv3x3_wstream_f16 / vd_gemm_wstream_f16 return today.
 int vd_gemm_normalise(const VdGemmDesc* desc, void* gemm_args_out) {
     int cfg = 0, ns = 1;
     return plan_gemm(desc, *static_cast<GemmArgs*>(gemm_args_out), cfg, ns);
 }
-// sum `nsplit` fp32 slabs of d.ws and run the fused epilogue of the (normalised) descriptor; with d.out_stats also the
-// per-channel statistics in partials of 64 rows
+// launch_reduce for a (normalised, batch 1) descriptor of the weight-streaming entry points
 int vd_gemm_launch_reduce(const void* gemm_args, int nsplit, hipStream_t stream) {
-    const GemmArgs& a = *static_cast<const GemmArgs*>(gemm_args);
-    const VdGemmDesc& d = a.d;
-    if (d.out_stats != nullptr) {
-        launch_reduce_stats(a, nsplit, stream);
-        return vd_check_launch("splitk_reduce_stats");
-    }
-    const size_t total = (size_t)d.M * ((d.N + 7) / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, 1), dim3(256), 0, stream, a, nsplit);
-    return vd_check_launch("splitk_reduce");
+    return launch_reduce(*static_cast<const GemmArgs*>(gemm_args), nsplit, 1, stream, false);
 }

@@ -1,5 +1,5 @@
-// fp16 MFMA GEMM / implicit-GEMM convolution kernel template for gfx950 (CDNA4).  Included by gemm.hip (planner,
-// 2-waves-per-SIMD instances) and gemm_big.hip (one-wave-per-SIMD instances with large per-wave tiles).
+// fp16 MFMA GEMM / implicit-GEMM convolution kernel template for gfx950 (CDNA4).  Included by gemm.hip (planner and the
+// table of built instances).
 //
 //   out[m][n] = epilogue( sum_k A[m][k] * W[n][k] )
 //
@@ -18,16 +18,17 @@
 //   * K is walked in KB-deep tiles through a ring of STAGES LDS buffers.  Tiles travel global -> LDS by LDS-DMA
 //     (buffer_load ... lds: no VGPR round trip, no ds_write); the XOR swizzle of the LDS image is applied on the source
 //     side.  Default main loop ("burst"): wait for tile i, barrier, issue ALL DMA instructions of tile i + STAGES - 1,
-//     then the fragment reads and MFMAs of tile i.  -DVD_GEMM_PIPELINED builds the software-pipelined alternative (DMA
-//     issued in 1-KiB pieces between MFMA groups, operand fragments double-buffered across the per-tile barrier): faster
-//     in a warm sweep, 4 % slower inside the UNet forward where weights stream cold from HBM.
+//     then the fragment reads and MFMAs of tile i.  (The software-pipelined alternative of rounds 1-5 -- DMA issued in
+//     1-KiB pieces between MFMA groups, operand fragments double-buffered across the per-tile barrier -- was faster in a
+//     warm sweep and 4 % slower inside the UNet forward where weights stream cold from HBM, DESIGN.md section 2.1;
+//     removed in round 6.)
 //   * v_mfma_f32_32x32x16_f16, fp32 accumulation, operands swapped (MFMA A operand = W rows, B operand = activation
 //     rows) so a lane owns ONE output row and 4 consecutive columns per register group: bias / LayerNorm fold /
 //     activation / GEGLU gating / alpha run in registers, the tile is staged through LDS and leaves as 16-byte row
 //     segments with the per-batch row vector and the residual added on the way out.
 //   * Larger wave tiles cut LDS traffic per MFMA (reads: (MI+NI)/(MI*NI) KiB per MFMA; DMA writes: (BM+BN)*KB*2 bytes per
-//     tile): the one-wave-per-SIMD and 64x128 / 64x160-per-wave instances of gemm_big.hip exist for that and for the
-//     experiments DESIGN.md reports; the UNet's shapes do not reward them.
+//     tile): the one-wave-per-SIMD and 64x128 / 64x160-per-wave instances of rounds 1-5 existed for that and for the
+//     experiments DESIGN.md reports; the UNet's shapes do not reward them (removed in round 6, gemm.hip keeps their slots).
 //   * LayerNorm fold (LNF instances): (mean, rstd) per row from d.ln_stats, the block's colsum slice from LDS.
 //   * split-K: fp32 slabs + splitk_reduce_kernel (gemm.hip); optional in-kernel reduction by the last-arriving block
 //     (d.sync, agent-scope atomics) -- correct, slower, off by default.
@@ -1191,25 +1192,11 @@ int launch_cfg(const GemmArgs& a, int nsplit, hipStream_t stream) {
     }
     constexpr int LDS = gemm_lds_bytes<BM, BN, NT, STAGES, KB>() + (LNF ? BN * 4 : 0);   // + the block's colsum entries
     static_assert(LDS <= 160 * 1024, "tile does not fit the CU's LDS");
-    // the dynamic-LDS attribute is per device: one bit per device ordinal, set idempotently (safe under concurrent callers)
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_kernel<BM, BN, WM, WN, NT, STAGES, KB, OCC, LNF, MID>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            vd_set_error("vd_gemm_f16: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&gemm_f16_kernel<BM, BN, WM, WN, NT, STAGES, KB, OCC, LNF, MID>}, LDS, done, "vd_gemm_f16")) return rc;
     dim3 grid(a.tiles_m * a.tiles_n, nsplit, a.d.batch > 0 ? a.d.batch : 1);
     hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, WM, WN, NT, STAGES, KB, OCC, LNF, MID>), grid, dim3(NT), LDS, stream, a);
     return vd_check_launch("vd_gemm_f16");
 }
 
 }  // namespace
-
-// one-wave-per-SIMD instances (gemm_big.hip); cfg = TileCfg value

@@ -500,17 +500,7 @@ __global__ __launch_bounds__(512, 2) void rowchain320_kernel(const RCArgs p) {
 template <bool LN, bool MULTI>
 int launch_rowgemm(const RGArgs& a, hipStream_t stream) {
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm320_kernel<LN, MULTI>), hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS + (MULTI ? RG_MULTI_EXTRA : 0));
-        if (e != hipSuccess) {
-            vd_set_error("vd_gemm_row320_f16: cannot reserve %d bytes of LDS: %s", RG_LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&rowgemm320_kernel<LN, MULTI>}, RG_LDS + (MULTI ? RG_MULTI_EXTRA : 0), done, "vd_gemm_row320_f16", RG_LDS)) return rc;
     const dim3 grid((unsigned)((a.M + RG_BM - 1) / RG_BM), MULTI ? 1u : (unsigned)(a.N / RG_C));
     constexpr int LDS = RG_LDS + (MULTI ? RG_MULTI_EXTRA : 0);
     hipLaunchKernelGGL((rowgemm320_kernel<LN, MULTI>), grid, dim3(512), LDS, stream, a);
@@ -558,17 +548,7 @@ extern "C" int vd_gemm_row320_chain_f16(const void* x, const void* gn_scale, con
                "vd_gemm_row320_chain_f16: operands must be 16-byte aligned");
     constexpr int LDS = RG_LDS + RG_MULTI_EXTRA;
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rowchain320_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            vd_set_error("vd_gemm_row320_chain_f16: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&rowchain320_kernel}, LDS, done, "vd_gemm_row320_chain_f16")) return rc;
     RCArgs a;
     a.x = (const f16*)x; a.sc = (const f16*)gn_scale; a.sh = (const f16*)gn_shift; a.ctr = (const f16*)gn_center; a.w1 = (const f16*)w1; a.b1 = (const f16*)b1;
     a.h = (f16*)h; a.w2 = (const f16*)w2; a.b2 = (const f16*)b2; a.y2 = (f16*)y2;

@@ -327,16 +327,8 @@ extern "C" int vd_adjust_rank_f16(const void* x, void* y, int B, int L, int C, i
     hipLaunchKernelGGL(ar_center_kernel, dim3(L, B), dim3(256), 0, stream, (const f16*)x, A, mean, rs1, L, C);
     hipLaunchKernelGGL(ar_gram_kernel, dim3((L + 15) / 16, (L + 15) / 16, B), dim3(256), 0, stream, A, G, L, C);
     const size_t lds = ((size_t)2 * L * PS + 2 * P * PS + 2 * P) * sizeof(float);
-    static bool attr_done = false;  // idempotent; a race only repeats the call
-    if (!attr_done) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_eig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(((size_t)2 * 512 * PS + 2 * P * PS + 2 * P) * sizeof(float)));
-        if (e != hipSuccess) {
-            vd_set_error("vd_adjust_rank_f16: cannot reserve LDS: %s", hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        attr_done = true;
-    }
+    static std::atomic<unsigned long long> done{0};   // reserved for the largest L the entry point takes
+    if (const int rc = vd_reserve_lds({(const void*)&ar_eig_kernel}, (int)(((size_t)2 * 512 * PS + 2 * P * PS + 2 * P) * sizeof(float)), done, "vd_adjust_rank_f16", -1)) return rc;
     hipLaunchKernelGGL(ar_eig_kernel, dim3(B), dim3(1024), lds, stream, G, U, L, q, iters);
     hipLaunchKernelGGL(ar_z_kernel, dim3((C + 255) / 256, q, B), dim3(256), 0, stream, A, U, Z, L, C, q);
     hipLaunchKernelGGL(ar_combine_kernel, dim3(L, B), dim3(256), 0, stream, A, U, Z, mean, g, keep, rs2, L, C, q);

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
 
 typedef _Float16 f16;
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
@@ -34,6 +36,29 @@ inline int vd_rescale_args_ok(const char* what, int64_t n, int64_t per_sample, i
     VD_REQUIRE(n % per_sample == 0, "%s: n = %lld is not a multiple of per_sample = %lld", what, (long long)n,
                (long long)per_sample);
     return VD_OK;
+}
+
+// Host only.  Raise the dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) of `kernels` to `bytes`, once per device: the
+// attribute is per device, `done` is the caller's static mask with one bit per device ordinal, set idempotently (safe under
+// concurrent callers: a race only repeats the call).  what: the entry point's name for the error text; text_bytes: the byte count
+// that text gives (< 0: none).
+inline int vd_reserve_lds(std::initializer_list<const void*> kernels, int bytes, std::atomic<unsigned long long>& done, const char* what, int text_bytes) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return VD_OK;
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess) continue;
+        if (text_bytes < 0) vd_set_error("%s: cannot reserve LDS: %s", what, hipGetErrorString(e));
+        else vd_set_error("%s: cannot reserve %d bytes of LDS: %s", what, text_bytes, hipGetErrorString(e));
+        return VD_ERR_LAUNCH;
+    }
+    done.fetch_or(bit, std::memory_order_release);
+    return VD_OK;
+}
+inline int vd_reserve_lds(std::initializer_list<const void*> kernels, int bytes, std::atomic<unsigned long long>& done, const char* what) {
+    return vd_reserve_lds(kernels, bytes, done, what, bytes);
 }
 
 // blocks of a grid-stride launch over n work items

@@ -431,17 +431,7 @@ int launch_xattn(XAttnArgs a, hipStream_t stream) {
     static_assert(LDS * OCC <= 160 * 1024, "LDS budget at the requested occupancy");
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_kernel<D, NST, EK, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            vd_set_error("vd_xattn_f16: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(e));
-            return VD_ERR_LAUNCH;
-        }
-        done.fetch_or(bit, std::memory_order_release);
-    }
+    if (const int rc = vd_reserve_lds({(const void*)&xattn_kernel<D, NST, EK, OCC>}, LDS, done, "vd_xattn_f16")) return rc;
     a.nqb = (a.Nq + 127) / 128;
     a.xcd_map = ((a.B * a.nqb) & 7) == 0 ? 1 : 0;
     hipLaunchKernelGGL((xattn_kernel<D, NST, EK, OCC>), dim3(a.nqb * a.B * a.H), dim3(256), LDS, stream, a);
