@@ -211,6 +211,26 @@ int vd_conv3x3_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 int vd_gemm_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 /* Development hook: kernel instance (0 = default) and the grid size the split over chunks aims for (256). Process-global. */
 int vd_conv3x3_wstream_set_variant(int variant, int target_blocks);
+/* The 3x3 / stride 1 / pad 1 convolution behind a nearest-2x upsample (VdGemmDesc.ups = 1: Upsample.conv of the UNet and of the
+ * VAE decoder, lib/model_zoo/openaimodel.py:89-117, autokl_modules.py:42-56) as four 2x2 PHASE convolutions of the
+ * low-resolution image.  Output pixel (2i + a, 2j + b), a, b in {0, 1}, sees only a 2x2 window of source pixels; the 3x3 weights
+ * that meet the same source pixel are summed once at pack time:
+ *     out[2i + a][2j + b][n] = sum_{p, q in {0, 1}} sum_c Wph[a][b][n][p][q][c] x[i + a - 1 + p][j + b - 1 + q][c]
+ *     Wph[a][b][n][p][q][c]  = sum_{ky in R(a, p)} sum_{kx in R(b, q)} w[n][ky][kx][c]
+ *     R(0, 0) = {0}, R(0, 1) = {1, 2}, R(1, 0) = {0, 1}, R(1, 1) = {2};  source indices outside the image read zero
+ * so the launch executes 4 / 9 of the multiplies of the upsampled form.  The sums are exact algebra with ONE added rounding: w_phase
+ * (fp16 [4 phases = 2a + b][N][4 taps = 2p + q][C], vd_hip/pack.py: pack_conv_weight_ups_phase) holds the fp32 sums of the fp16
+ * weights rounded to fp16 once, so results agree with vd_gemm_f16 on the same descriptor to that rounding (bit for bit where
+ * every sum is exact), not bit for bit in general.  `desc` as for vd_gemm_f16 (single source, ups = 1, its `w` is validated but
+ * not read; every epilogue of the halo-resident convolution, out_stats / stat_sums included); the TAPS = 4 instances of
+ * conv3x3_halo_kernel run it, split over channel chunks + the split-K reduce where the grid is small (needs desc->ws).
+ * vd_conv3x3_ups_phase_supported: 1 when desc's geometry fits (else the caller stays on vd_gemm_f16).
+ * vd_conv3x3_ups_phase_plan: the instance (vd_conv3x3_ups_phase_name), the split factor (set VdGemmDesc.split_k to it before
+ * sizing the workspace) and the rows per out_stats partial (0: none) the launch will use. */
+int vd_conv3x3_ups_phase_supported(const VdGemmDesc* desc);
+int vd_conv3x3_ups_phase_plan(const VdGemmDesc* desc, int* variant, int* nsplit, int* stat_rows);
+const char* vd_conv3x3_ups_phase_name(int variant);
+int vd_conv3x3_ups_phase_f16(const VdGemmDesc* desc, const void* w_phase, hipStream_t stream);
 /* (a tile_cfg that is not built is refused: non-zero return, table unchanged) */
 int vd_gemm_tune_set(int M, int N, int K, int ksize, int epi_class, int tile_cfg, int nsplit);
 int vd_gemm_tune_clear(void);

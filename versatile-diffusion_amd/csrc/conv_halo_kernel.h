@@ -63,7 +63,16 @@ struct ConvHaloArgs {
 // MODE: 2 (the only main loop left, see above).  NT = 64 * waves; wave grid (BM / WM) x (BN / WN), wave tile WM pixels x WN channels.
 // SKIP (round 4): behind the 3x3 chunks the block multiplies the chunks of a 1x1 convolution of a second (two-source) input on
 // the same pixels into the same accumulators -- ResBlock's skip_connection(x) + h as extra K of the second conv (d.skip_*).
-template <int BM, int BN, int WM, int WN, int NT, int MODE, bool SKIP = false>
+//
+// TAPS = 4: the PHASE form of the conv behind a nearest-2x upsample.  Output pixel (2i + a, 2j + b) of phase (a, b) is a
+// 2x2 convolution of the LOW-RESOLUTION image, out = sum_{p, q in {0, 1}} Wph[a][b][n][p][q][:] . x[i + a - 1 + p][j + b - 1 + q][:], with
+// the 3x3 weights that meet the same source pixel summed once at pack time (vd_hip/pack.py: pack_conv_weight_ups_phase, fp16
+// [4 phases][N][2x2 taps][C]): 4 / 9 of the MFMAs.  The launcher describes the low-resolution grid (Hv = Hin, ups = 0, pitch =
+// tw + 1, rg + 1 halo rows) with 4x the row tiles, phase slowest; a block owns one phase of one low-resolution patch: its halo
+// origin is shifted by (a - 1, b - 1), tap (p, q) is the view at pixel + p * pitch + q, its weight tiles come from the phase's
+// [N][4 C] matrix, and tile row (y, x) leaves as output pixel (2 y + a, 2 x + b).  Same loop, barriers and request order; the
+// weight stage of a tap is (4 chunk + tap) % 3, a running value instead of a constant.  No SKIP form (an upsample conv has one source).
+template <int BM, int BN, int WM, int WN, int NT, int MODE, bool SKIP = false, int TAPS = 9>
 __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHaloArgs p) {
     VD_TL_DECL;
     VD_TL(0);
@@ -79,8 +88,10 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     constexpr int HPXMAX = BM * 100 / 64 + 16;          // bound on halo pixels (checked by the launcher)
     constexpr int NHP = (HPXMAX + 7) / 8;               // halo pieces of 8 pixels
     constexpr int HPW = (NHP + NW - 1) / NW;            // ... per wave and chunk
-    constexpr int HPT = (HPW + 7) / 8;                  // ... per wave and tap (taps 0..7 carry them)
-    constexpr int MAXHP = HPT * 8;
+    constexpr int HPT = (HPW + TAPS - 2) / (TAPS - 1);  // ... per wave and tap (every tap but the last carries them)
+    constexpr int MAXHP = HPT * (TAPS - 1);
+    static_assert(TAPS == 9 || (TAPS == 4 && !SKIP), "3x3, or the 2x2 phase form of an upsample conv");
+    constexpr bool PHASE = TAPS == 4;
     constexpr int CS_LD = BN + 8;                       // fp16 epilogue tile leading dimension
     static_assert(BN % 8 == 0 && WM % 32 == 0 && WN % 32 == 0, "tile shape");
 
@@ -102,10 +113,14 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
         const int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, idx = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const int tm = p.g.mfast ? bid % p.g.tiles_m : bid / p.g.tiles_n;   // see gemm_f16_kernel: which operand an XCD keeps
-    const int tn = p.g.mfast ? bid / p.g.tiles_m : bid - tm * p.g.tiles_n;
+    const int tm_all = p.g.mfast ? bid % p.g.tiles_m : bid / p.g.tiles_n;   // see gemm_f16_kernel: which operand an XCD keeps
+    const int tn = p.g.mfast ? bid / p.g.tiles_m : bid - tm_all * p.g.tiles_n;
     const int n0 = tn * BN;
     const int split = blockIdx.y;
+    // PHASE: row tiles are [phase = 2 a + b][low-resolution patch]
+    const int phase = PHASE ? tm_all / (p.g.tiles_m >> 2) : 0;
+    const int tm = PHASE ? tm_all - phase * (p.g.tiles_m >> 2) : tm_all;
+    const int pa = phase >> 1, pb = phase & 1;
 
     // patch origin
     int img0, y0, x0;
@@ -141,7 +156,7 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
         const int rem = hp - grp * p.gpx;
         const int hy = (rem * p.mg_pitch) >> 20;
         const int hx = rem - hy * p.pitch;
-        const int vy = y0 + hy - 1, vx = x0 + hx - 1;
+        const int vy = y0 + hy + pa - 1, vx = x0 + hx + pb - 1;   // (pa = pb = 0 unless PHASE)
         const bool ok = hp < p.hpx && (unsigned)vy < (unsigned)p.Hv && (unsigned)vx < (unsigned)p.Wv;
         const int pix = ((img0 + grp) * d.Hin + (vy >> d.ups)) * d.Win + (vx >> d.ups);
         const int slot = (lane & 7) ^ ((hp >> 1) & 7);
@@ -158,6 +173,7 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     }
 
     const int ctot = d.c0 + d.c1;
+    const unsigned w_phase_off = PHASE ? (unsigned)phase * (unsigned)d.N * (unsigned)d.ldw * 2u : 0u;   // the phase's [N][4 C] matrix
     const int c_begin = split * p.chunks_per_split;
     int c_end = c_begin + p.chunks_per_split;
     if (c_end > p.nchunks) c_end = p.nchunks;
@@ -186,7 +202,7 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     };
     auto issue_w = [&](int c, int tap, int stage) {   // weight tile of (chunk c, tap) -> stage
         if (!dma_on) return;
-        const unsigned soff = (unsigned)((tap * ctot + c * 64) * 2);
+        const unsigned soff = (unsigned)((tap * ctot + c * 64) * 2) + w_phase_off;
 #pragma unroll
         for (int j = 0; j < WPW; ++j) {
             const int q = j * NW + wave_s;
@@ -255,7 +271,16 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
             for (int j = 0; j < NI; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[j], a[i], acc[i][j], 0, 0, 0);
     };
-    auto tapoff_of = [&](int t) { return (t / 3) * p.pitch + (t % 3); };
+    auto tapoff_of = [&](int t) { return PHASE ? (t >> 1) * p.pitch + (t & 1) : (t / 3) * p.pitch + (t % 3); };
+    // weight stage of tap t (0 .. TAPS + 1: up to two taps ahead) of the current chunk = (TAPS * chunk + t) % 3
+    int stage0 = 0;   // (TAPS * chunk) % 3: stays 0 for 9 taps
+    auto stage_of = [&](int t) {
+        if constexpr (TAPS % 3 == 0) return t % 3;
+        else {
+            const int s = stage0 + t % 3;
+            return s >= 3 ? s - 3 : s;
+        }
+    };
 
     // ---- prologue: the whole halo of the first chunk and the first weight tile(s)
     {
@@ -292,10 +317,9 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
                 hrow[i] = hp_base[i];
                 asm volatile("" : "+v"(hrow[i]));
             }
-            static_for<0, 9>([&](auto tt) {
+            static_for<0, TAPS>([&](auto tt) {
                 constexpr int t = decltype(tt)::value;
-                constexpr int stage = t % 3;   // (9 lc + t) % 3
-                const char* wst = w_smem + stage * WSTAGE;
+                const char* wst = w_smem + stage_of(t) * WSTAGE;
                 const TapAddr ta = tap_addr(halo_off, tapoff_of(t));
                 auto pin = [&]() { __builtin_amdgcn_sched_barrier(0); };
                 read_frags(wst, ta, 1, a1f, w1f);
@@ -310,25 +334,26 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
                 wait_vm<0>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                if constexpr (t + 2 < 9) issue_w(c, t + 2, (t + 2) % 3);
-                else if (more) issue_w(c + 1, t + 2 - 9, (t + 2) % 3);
-                if constexpr (t < 8) {
+                if constexpr (t + 2 < TAPS) issue_w(c, t + 2, stage_of(t + 2));
+                else if (more) issue_w(c + 1, t + 2 - TAPS, stage_of(t + 2));
+                if constexpr (t < TAPS - 1) {
                     if (more) static_for<t * HPT, (t + 1) * HPT>([&](auto jt) { issue_halo(jt, csn, nxt_halo); });
                 }
                 read_frags(wst, ta, 3, a1f, w1f);
                 pin();
                 mma(a0f, w0f);
                 pin();
-                if constexpr (t < 8) {
+                if constexpr (t < TAPS - 1) {
                     const TapAddr tn_ = tap_addr(halo_off, tapoff_of(t + 1));
-                    read_frags(w_smem + ((t + 1) % 3) * WSTAGE, tn_, 0, a0f, w0f);
+                    read_frags(w_smem + stage_of(t + 1) * WSTAGE, tn_, 0, a0f, w0f);
                 } else if (more) {
                     const TapAddr tn_ = tap_addr(halo_off ^ p.halo_bytes, 0);
-                    read_frags(w_smem, tn_, 0, a0f, w0f);
+                    read_frags(w_smem + stage_of(TAPS) * WSTAGE, tn_, 0, a0f, w0f);
                 }
                 pin();
                 mma(a1f, w1f);
             });
+            stage0 = stage_of(TAPS);
         }
     }
     if constexpr (SKIP) {
@@ -402,7 +427,8 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     auto out_row = [&](int m) {
         const int grp = m >> p.lgsz;
         const int r = m - (grp << p.lgsz);
-        return ((img0 + grp) * p.Hv + y0 + (r >> p.ltw)) * p.Wv + x0 + (r & (p.tw - 1));
+        if constexpr (PHASE) return ((img0 + grp) * 2 * p.Hv + 2 * (y0 + (r >> p.ltw)) + pa) * 2 * p.Wv + 2 * (x0 + (r & (p.tw - 1))) + pb;
+        else return ((img0 + grp) * p.Hv + y0 + (r >> p.ltw)) * p.Wv + x0 + (r & (p.tw - 1));
     };
 
     // ---- split over channel chunks: fp32 slabs for splitk_reduce_kernel, straight from registers
@@ -436,7 +462,7 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     const bool want_res = (e.flags & VD_EPI_RESIDUAL) != 0;
     const bool want_rv = (e.flags & VD_EPI_ROWVEC) != 0;
     const bool ld_ok = ((e.ldr & 7) == 0) && ((e.ldc & 7) == 0);
-    const bool rv_per_image = e.rows_per_batch == p.Hv * p.Wv;
+    const bool rv_per_image = e.rows_per_batch == (PHASE ? 4 : 1) * p.Hv * p.Wv;
     // d.out_stats: per-channel statistics of the stored tile for a consuming GroupNorm (gemm_kernel.h: emit_chan_stats);
     // part 2 then writes what it stores back into the tile
     const bool want_stats = d.out_stats != nullptr && p.g.stat_rows > 0;
@@ -569,9 +595,12 @@ __global__ __launch_bounds__(NT, NT / 256) void conv3x3_halo_kernel(const ConvHa
     // one partial per patch (a patch lies in one image), or per image where a patch holds several whole small images
     if (want_stats) {
         __syncthreads();
+        // PHASE: the R rows of a sub-block are one phase of R low-resolution pixels = a quarter of 4 R output pixels of one image:
+        // partial 4 (low-resolution sub-block) + phase, so an image owns the same run of HW / R partials as in the 3x3 form
         const int nsub = p.ngrp, R = BM / p.ngrp;
         emit_chan_stats<BN, CS_LD, NT>(cs, reinterpret_cast<float*>(smem + BM * CS_LD * 2), tid, R, nsub, nsub, d.out_stats,
-                                       (size_t)tm * nsub, d.N, n0, reinterpret_cast<unsigned long long*>(d.stat_sums), d.stat_img_rows);
+                                       PHASE ? (size_t)tm * nsub * 4 + phase : (size_t)tm * nsub, d.N, n0,
+                                       reinterpret_cast<unsigned long long*>(d.stat_sums), d.stat_img_rows, PHASE ? 4 : 1);
     }
     VD_TL(4);   // (behind the statistics pass where one runs)
     VD_TL_FLUSH(p.g.tl);
@@ -584,7 +613,7 @@ enum HaloVariantId {
     HALO_SKIP = 12      // HALO_PLANNER with the folded 1x1 skip convolution
 };
 
-template <int BM, int BN, int WM, int WN, int NT, int MODE, bool SKIP = false>
+template <int BM, int BN, int WM, int WN, int NT, int MODE, bool SKIP = false, int TAPS = 9>
 int launch_conv_halo(const ConvHaloArgs& a, int nsplit, hipStream_t stream) {
     constexpr int WST = 3;
     constexpr int EPI = stat_lds_bytes(BM, BN);   // epilogue tile + the lane scratch of the statistics pass
@@ -595,9 +624,9 @@ int launch_conv_halo(const ConvHaloArgs& a, int nsplit, hipStream_t stream) {
         return VD_ERR_UNSUPPORTED;
     }
     static std::atomic<unsigned long long> done{0};
-    if (const int rc = vd_reserve_lds({(const void*)&conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP>}, 160 * 1024, done, "conv3x3_halo", -1)) return rc;
+    if (const int rc = vd_reserve_lds({(const void*)&conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP, TAPS>}, 160 * 1024, done, "conv3x3_halo", -1)) return rc;
     dim3 grid(a.g.tiles_m * a.g.tiles_n, nsplit, 1);
-    hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP>), grid, dim3(NT), lds, stream, a);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WM, WN, NT, MODE, SKIP, TAPS>), grid, dim3(NT), lds, stream, a);
     return vd_check_launch("conv3x3_halo");
 }
 

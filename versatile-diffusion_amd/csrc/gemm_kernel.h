@@ -275,7 +275,8 @@ __device__ __forceinline__ void gn_sums_add(unsigned long long* sums, size_t img
 
 template <int BN, int CS_LD, int NT>
 __device__ __forceinline__ void emit_chan_stats(const f16* cs, float* red, int tid, int R, int nsub, int pvalid, float* out,
-                                                size_t pbase, int N, int n0, unsigned long long* sums = nullptr, int img_rows = 0) {
+                                                size_t pbase, int N, int n0, unsigned long long* sums = nullptr, int img_rows = 0,
+                                                int pstride = 1) {
     constexpr int OCT = BN / 8;
     constexpr int LANES = stat_lanes(BN);
     const int co = tid % OCT, rl = tid / OCT;
@@ -314,8 +315,9 @@ __device__ __forceinline__ void emit_chan_stats(const f16* cs, float* red, int t
                     }
                     const float n = (float)R;
                     const float mean = (float)base[c] + S / n, m2 = fmaxf(Q - S * S / n, 0.f);
-                    *reinterpret_cast<float2*>(out + ((pbase + s) * (size_t)N + n0 + c) * 2) = make_float2(mean, m2);
-                    if (sums != nullptr) gn_sums_add(sums, ((pbase + s) * (size_t)R) / (size_t)img_rows, N, n0 + c, mean, m2, R);
+                    const size_t pi = pbase + (size_t)s * pstride;   // partial index (pstride: the phase form of conv3x3_halo_kernel)
+                    *reinterpret_cast<float2*>(out + (pi * (size_t)N + n0 + c) * 2) = make_float2(mean, m2);
+                    if (sums != nullptr) gn_sums_add(sums, (pi * (size_t)R) / (size_t)img_rows, N, n0 + c, mean, m2, R);
                 }
             }
         }

@@ -13,9 +13,8 @@
 //   2. vd_gn_table_f32 folds the partials of one (sample, group) with Chan's parallel-variance update and writes the
 //      normalisation as a per-(sample, channel) affine map  y = x * scale + shift,  scale = rstd * gamma,
 //      shift = beta - mean * rstd * gamma  (fp32 [B][2][C]): a few KB, one tiny launch.
-//   3. The map (+ SiLU) is applied by the CONSUMER: conv3x3_halo_kernel transforms the input halo in LDS once per
-//      64-channel chunk (VdGemmDesc.in_norm, conv_halo_kernel.h), so the normalised activation never exists in HBM;
-//      vd_gn_apply_table_f16 is the one-read one-write elementwise form for consumers without that path.
+//   3. The map (+ SiLU) is applied by vd_gn_apply_table_f16, the one-read one-write elementwise launch in front of the
+//      consumer.  (No convolution applies it to its own input halo: VdGemmDesc has no such operand.)
 // Numerics: partial sums run over (x - k) with k = the block's first row of that channel (a sample, hence within a few
 // sigma of the mean), so M2 = S2 - S1^2 / n does not cancel when |mean| >> sigma; partials are combined as
 // M2 = sum M2_i + sum n_i (mean_i - mean)^2 in fp32 (torch's Welford / two-pass robustness, see

@@ -87,6 +87,11 @@ class Conv2d(nn.Conv2d, PackCache):
         """MFMA-fragment-ordered copy of the 3x3 weights for the weight-streaming kernel of the 8x8 level."""
         return self._packed("w_stream", (self.weight,), lambda: pack.pack_conv_weight_stream(_h(self.weight)))
 
+    def _w_phase(self):
+        """The 3x3 weights summed per output phase of a nearest-2x upsample (vd_conv3x3_ups_phase_f16): exact algebra with one
+        added weight rounding (fp32 sums of the fp16 weights, rounded to fp16 once)."""
+        return self._packed("w_phase", (self.weight,), lambda: pack.pack_conv_weight_ups_phase(_h(self.weight)))
+
     def _w_stream_1x1(self):
         """Fragment-ordered copy of a 1x1 conv's weights (folded skip convolution of the weight-streaming kernel)."""
         return self._packed("w_stream_1x1", (self.weight,),
@@ -114,6 +119,8 @@ class Conv2d(nn.Conv2d, PackCache):
                      and self.out_channels % 256 == 0)   # 8x8 level: the layer is its weight stream
             if small:
                 epi = dict(epi, w_stream=self._w_stream())
+            if ops.UPS_PHASE and ups == 1 and x1 is None:   # four 2x2 phase convolutions of the low-resolution image
+                epi = dict(epi, w_phase=self._w_phase())
         return ops.conv2d_nhwc(x, w, b, ksize=k, stride=s, pad=p, ups=ups, x1=x1, pad_hi=pad_hi, **epi)
 
 

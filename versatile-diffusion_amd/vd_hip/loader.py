@@ -64,6 +64,11 @@ PROTOTYPES = {
     "vd_gemm_wstream_f16": (_I, [ctypes.POINTER(VdGemmDesc), _P, _P]),
     "vd_conv3x3_wstream_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),
     "vd_conv3x3_wstream_set_variant": (_I, [_I, _I]),
+    "vd_conv3x3_ups_phase_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),
+    "vd_conv3x3_ups_phase_plan": (_I, [ctypes.POINTER(VdGemmDesc), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(ctypes.c_int)]),
+    "vd_conv3x3_ups_phase_name": (ctypes.c_char_p, [_I]),
+    "vd_conv3x3_ups_phase_f16": (_I, [ctypes.POINTER(VdGemmDesc), _P, _P]),
     "vd_gemm_config_name": (ctypes.c_char_p, [_I]),
     "vd_gemm_num_configs": (_I, []),
     "vd_gemm_set_override": (_I, [_I]),

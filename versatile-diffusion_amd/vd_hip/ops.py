@@ -178,7 +178,7 @@ def repeat_batch(t, repeat):
 def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, out=None, M=None, N=None, K=None,
          conv=None, act=ACT_NONE, alpha=1.0, out_f32=False, bias_along_m=False, batch=1, strides=(0, 0, 0, 0),
          lda0=0, lda1=0, ldw=0, ldc=0, ldr=0, c0=0, c1=0, split_k=0, out_shape=None, colsum=None, ln_eps=0.0, fixup=None,
-         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None):
+         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None, w_phase=None):
     """out = epilogue(A @ W^T); see VdGemmDesc in include/vd_hip.h.
 
     conv = dict(Hin, Win, Hout, Wout, ksize, stride, pad, ups) selects the implicit-GEMM gather.
@@ -337,6 +337,39 @@ def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, 
         if stats is not None:
             out._vd_stats = stats
         return out
+    if (w_phase is not None and UPS_PHASE and conv is not None and conv.get("ups", 0) == 1 and a1 is None and colsum is None and skip is None
+            and row_sums is None and not out_f32 and max(batch, 1) == 1 and lib().vd_conv3x3_ups_phase_supported(ctypes.byref(d))):
+        # upsample conv in its phase form: K = 4 C per output instead of 9 C (geometry that does not fit stays on vd_gemm_f16 below)
+        _req(w_phase, "w_phase")
+        if tuple(w_phase.shape) != (4, int(N), 4 * d.c0):
+            raise VdHipError("gemm: w_phase does not match N=%d C=%d" % (int(N), d.c0))
+        d.split_k = int(split_k)
+        pv, pns, prow = ctypes.c_int(0), ctypes.c_int(1), ctypes.c_int(0)
+        d.stat_img_rows = int(stat_img_rows)
+        _check(lib().vd_conv3x3_ups_phase_plan(ctypes.byref(d), ctypes.byref(pv), ctypes.byref(pns), ctypes.byref(prow)))
+        if pns.value > 1:
+            d.split_k = pns.value
+            d.ws = workspace(lib().vd_gemm_workspace_bytes(ctypes.byref(d)), a0.device, "gemm").data_ptr()
+        stats = None
+        if want_stats and prow.value > 0:
+            hw = int(stat_img_rows) if stat_img_rows else int(d.Hout) * int(d.Wout)
+            sbuf = torch.empty((int(M) // prow.value, n_out, 2), dtype=torch.float32, device=a0.device)
+            d.out_stats = sbuf.data_ptr()
+            stats = ChanStats(sbuf, hw // prow.value, n_out, hw, gn_sums_take(int(M) // hw, n_out, hw, a0.device))
+            if stats.sums is not None:
+                d.stat_img_rows = hw
+                d.stat_sums = stats.sums.data_ptr()
+        nm = lib().vd_conv3x3_ups_phase_name(pv.value).decode()
+        kp = 4 * d.c0   # the K this launch executes: 4 / 9 of the upsampled form's
+        if PROFILE_SHAPES:
+            nm += " M=%d N=%d K=%d ks=2 cls=0 split=%d" % (M, N, kp, pns.value)
+        extra = (float(M) * n_out if res is not None else 0.0) + (float(rowvec.numel()) if rowvec is not None else 0.0)
+        a_elems = float(conv["B"]) * conv["Hin"] * conv["Win"] * d.c0
+        with _Timed(nm, 2.0 * M * N * kp, 2.0 * (a_elems + 4.0 * N * kp + float(M) * n_out + extra)):
+            _check(lib().vd_conv3x3_ups_phase_f16(ctypes.byref(d), _ptr(w_phase), _stream()))
+        if stats is not None:
+            out._vd_stats = stats
+        return out
     # split-K (fp32 slabs + reduce) is the library's answer to small-M / deep-K problems: ask its planner first so
     # the workspace is sized for the split factor it will actually use
     name, d.ws = "gemm", None
@@ -457,6 +490,10 @@ def rowsum_take(rows, device):
 
 SKIP_FOLD = os.environ.get("VD_SKIP_FOLD", "1") != "0"   # ResBlock skip 1x1 convolution as extra K of the second 3x3 conv
 GEMM_WSTREAM = os.environ.get("VD_GEMM_WSTREAM", "1") != "0"   # long-K small-M Linear layers on gemm_wstream_kernel (FeedForward out at 16x16 / 8x8)
+# the 3x3 convolution behind a nearest-2x upsample as four 2x2 phase convolutions with pre-summed weights (vd_conv3x3_ups_phase_f16:
+# 4 / 9 of the multiplies; exact algebra with one added weight rounding, so not bit-identical to the upsampled form).  0 = the
+# upsampled 3x3 form on vd_gemm_f16
+UPS_PHASE = os.environ.get("VD_UPS_PHASE", "1") != "0"
 WSTREAM = os.environ.get("VD_WSTREAM", "1") != "0"   # development switch: 0 = the 8x8-level 3x3 convolutions stay on gemm_f16_kernel
 ROW320 = os.environ.get("VD_GEMM_ROW320", "1") != "0"   # development switch: 0 = the K = 320 projections stay on gemm_f16_kernel
 

@@ -8,6 +8,30 @@ def pack_conv_weight(w):
     return w.permute(0, 2, 3, 1).reshape(co, kh * kw * ci).contiguous()
 
 
+# taps (ky or kx, 0..2 for offsets -1..+1) of the 3x3 kernel that read source tap p (0, 1) of output phase a (0, 1) behind a
+# nearest-2x upsample: upsampled row 2i + a + ky - 1 is source row i + a - 1 + p
+UPS_PHASE_TAPS = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
+
+
+def pack_conv_weight_ups_phase(w):
+    """torch conv weight [Cout, Cin, 3, 3] -> [4 phases = 2a + b][Cout][4 taps = 2p + q][Cin] of vd_conv3x3_ups_phase_f16:
+    Wph[a][b][n][p][q][c] = sum over ky in UPS_PHASE_TAPS[a, p], kx in UPS_PHASE_TAPS[b, q] of w[n][c][ky][kx], summed in fp32
+    from the given (fp16) weights and rounded to their dtype ONCE.  conv(upsample2x(x), w) == the four 2x2 convolutions
+    out[2i + a][2j + b] = sum_{p, q} Wph[a][b][:, p, q] . x[i + a - 1 + p][j + b - 1 + q] exactly, up to that rounding."""
+    co, ci, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    wf = w.float() if w.dtype in (torch.float16, torch.bfloat16) else w   # (float64 in the tests of the algebra: no rounding at all)
+    out = wf.new_zeros((2, 2, co, 2, 2, ci))
+    for a in (0, 1):
+        for b in (0, 1):
+            for p in (0, 1):
+                for q in (0, 1):
+                    for ky in UPS_PHASE_TAPS[a, p]:
+                        for kx in UPS_PHASE_TAPS[b, q]:
+                            out[a, b, :, p, q, :] += wf[:, :, ky, kx]
+    return out.reshape(4, co, 4 * ci).to(w.dtype).contiguous()
+
+
 def pack_conv_weight_stream(w):
     """torch conv weight [Cout, Cin, 3, 3] -> MFMA-fragment order of vd_conv3x3_wstream_f16:
     [Cout / 32][Cin / 64][9 taps][4 k-steps][64 lanes][8], lane l of (n tile t, chunk c, tap, k-step s) holding
