@@ -304,7 +304,9 @@ typedef struct VdFfChain {
     int64_t M;
     int32_t C;
     float ln_eps, alpha;
-    int32_t reserved;
+    int32_t period_rows;    /* 0 (or M): off.  0 < period_rows < M: x (given a) and res hold period_rows rows and output row m reads
+                             * their row m % period_rows -- the replicas of a classifier-free-guidance batch share them.  Needs
+                             * stat_img_rows (rows of one image, % 128 == 0) dividing period_rows, and period_rows dividing M. */
 } VdFfChain;
 int vd_ff_chain_f16(const VdFfChain* chain, hipStream_t stream);
 int vd_ff_chain_supported(int C);
@@ -390,6 +392,13 @@ int vd_xattn_f16(const void* x, const void* wq, const void* bq, const float* col
                  const void* v, void* out, int B, int H, int Nq, int Nk, int D, int ldk, int ldv, int64_t sk, int64_t sv,
                  float scale, hipStream_t stream);
 int vd_xattn_supported(int H, int D);
+/* vd_xattn_f16 with x shared by the replicas of a sample: x is fp16 [x_samples][Nq][H*D] and sample b of k / v / out reads
+ * sample b % x_samples of it (B a multiple of x_samples; x_samples == B is vd_xattn_f16).  The batch the reference feeds under
+ * classifier-free guidance is [x; x] (lib/model_zoo/ddim.py:144-149): up to the first cross-attention the replicas are equal
+ * and need not be materialised. */
+int vd_xattn_rep_f16(const void* x, const void* wq, const void* bq, const float* colsum, float ln_eps, const void* k,
+                     const void* v, void* out, int B, int x_samples, int H, int Nq, int Nk, int D, int ldk, int ldv,
+                     int64_t sk, int64_t sv, float scale, hipStream_t stream);
 
 /* Row softmax fp32 [rows][n] -> fp16 (VAE AttnBlock, lib/model_zoo/autokl_modules.py:192). */
 int vd_softmax_rows_f32_f16(const float* s, void* p, int64_t rows, int n, hipStream_t stream);

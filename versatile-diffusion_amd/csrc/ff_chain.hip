@@ -60,9 +60,13 @@ struct FCArgs {
     int M;
     float eps, alpha;
     int nt_store;
+    int per_rows;      // REP instances: rows of the un-replicated x0 (PRE) and r (POST); output row m reads their row m % per_rows
 };
 
-template <bool PRE, bool POST>
+// REP: the residual operands x0 (PRE) and r (POST) are shared by the replicas of a sample (the [x; x] batch of classifier-free
+// guidance, not materialised).  per_rows is a multiple of 128, so a block's tile lies in one period and only the base of its
+// residual segments changes, once per block.
+template <bool PRE, bool POST, bool REP = false>
 __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -71,7 +75,9 @@ __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const int wm = wave >> 1, wn = wave & 1;
     const int hi = lane >> 5, l31 = lane & 31;
-    const int m0 = blockIdx.x * FC_BM;
+    // (REP: grid = (tiles of one replica, replicas) -- the replica index comes from the launch, not from a division)
+    const int m0 = REP ? blockIdx.y * p.per_rows + blockIdx.x * FC_BM : blockIdx.x * FC_BM;
+    const ptrdiff_t per_shift = REP ? -(ptrdiff_t)(blockIdx.y * p.per_rows) * FC_C : 0;   // residual row of output row m: m + per_shift / C
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     const i32x4 rs_w1 = make_rsrc_words(p.w1, (unsigned)(2 * FC_HID * FC_C * 2));
@@ -220,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
         zero_acc2();
         wait_vm<0>();
         __syncthreads();
-        const SegAdd x0seg = seg_request(p.x);   // the residual of this projection: in flight across its K loop
+        const SegAdd x0seg = seg_request(p.x + per_shift);   // the residual of this projection: in flight across its K loop
         proj_stage(p.wo);
         acc_to_tile(p.bo, 1.0f);
         wait_vm<0>();
@@ -426,7 +432,7 @@ __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
         zero_acc2();
         wait_vm<0>();
         __syncthreads();
-        const SegAdd rseg = seg_request(p.r);    // the residual of the last projection: in flight across its K loop
+        const SegAdd rseg = seg_request(p.r + per_shift);    // the residual of the last projection: in flight across its K loop
         proj_stage(p.wp);
         acc_to_tile(p.bp, p.alpha);
         wait_vm<0>();
@@ -442,11 +448,12 @@ __global__ __launch_bounds__(512, 2) void ff_chain_kernel(const FCArgs p) {
     }
 }
 
-template <bool PRE, bool POST>
+template <bool PRE, bool POST, bool REP = false>
 int launch_ffc(const FCArgs& a, hipStream_t stream) {
     static std::atomic<unsigned long long> done{0};
-    if (const int rc = vd_reserve_lds({(const void*)&ff_chain_kernel<PRE, POST>}, FC_LDS, done, "vd_ff_chain_f16")) return rc;
-    hipLaunchKernelGGL((ff_chain_kernel<PRE, POST>), dim3((unsigned)((a.M + FC_BM - 1) / FC_BM)), dim3(512), FC_LDS, stream, a);
+    if (const int rc = vd_reserve_lds({(const void*)&ff_chain_kernel<PRE, POST, REP>}, FC_LDS, done, "vd_ff_chain_f16")) return rc;
+    const dim3 grid = REP ? dim3((unsigned)(a.per_rows / FC_BM), (unsigned)(a.M / a.per_rows)) : dim3((unsigned)((a.M + FC_BM - 1) / FC_BM));
+    hipLaunchKernelGGL((ff_chain_kernel<PRE, POST, REP>), grid, dim3(512), FC_LDS, stream, a);
     return vd_check_launch("vd_ff_chain_f16");
 }
 
@@ -479,6 +486,18 @@ extern "C" int vd_ff_chain_f16(const VdFfChain* c, hipStream_t stream) {
     a.stat_sums = reinterpret_cast<unsigned long long*>(c->stat_sums); a.img_rows = (int)c->stat_img_rows;
     a.M = (int)c->M; a.eps = c->ln_eps; a.alpha = c->alpha;
     a.nt_store = 1;   // non-temporal stores of write-once outputs
+    a.per_rows = 0;
+    if (c->period_rows > 0 && c->period_rows < c->M) {
+        // x (with a) and res hold period_rows rows: whole images of stat_img_rows rows, which a 128-row tile must not straddle
+        VD_REQUIRE(c->stat_img_rows > 0 && c->stat_img_rows % FC_BM == 0 && c->period_rows % c->stat_img_rows == 0 && c->M % c->period_rows == 0,
+                   "vd_ff_chain_f16: period_rows %d needs whole images of stat_img_rows %ld rows (a multiple of 128) and M %ld a multiple of it",
+                   (int)c->period_rows, (long)c->stat_img_rows, (long)c->M);
+        a.per_rows = (int)c->period_rows;
+        if (pre && post) return launch_ffc<true, true, true>(a, stream);
+        if (pre) return launch_ffc<true, false, true>(a, stream);
+        return launch_ffc<false, true, true>(a, stream);
+    }
+    VD_REQUIRE(c->period_rows == 0 || c->period_rows == c->M, "vd_ff_chain_f16: period_rows %d outside 0 .. M", (int)c->period_rows);
     if (pre && post) return launch_ffc<true, true>(a, stream);
     if (pre) return launch_ffc<true, false>(a, stream);
     return launch_ffc<false, true>(a, stream);

@@ -45,6 +45,7 @@ struct XAttnArgs {
     int64_t sk, sv;
     float scale_log2, eps;
     int nqb, B, xcd_map;
+    int P;                // PER instances: x holds P samples, sample b of k / v / o reads sample b % P of x
 };
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -59,7 +60,9 @@ __device__ __forceinline__ void wait_vm_n() {
 
 // EK: the first K / V tile has its own LDS region and is requested before the projection starts (else both tiles alias the
 // projection stages and are requested when the projection is done).  OCC: blocks per CU the register budget allows.
-template <int D, int NST, bool EK, int OCC>
+// PER: x is shared by the B / P replicas of a sample (the [x; x] batch of classifier-free guidance, not materialised): only the
+// base of the block's x tile changes, computed once in front of the loops.
+template <int D, int NST, bool EK, int OCC, bool PER = false>
 __global__ __launch_bounds__(256, OCC) void xattn_kernel(const XAttnArgs p) {
     constexpr int QB = 128;
     constexpr int KS = (D + 15) / 16;       // k-steps of the QK^T MFMA
@@ -156,7 +159,8 @@ __global__ __launch_bounds__(256, OCC) void xattn_kernel(const XAttnArgs p) {
     if constexpr (EK) stage(0, 0);   // oldest request of the block: landed long before the projection is done
 
     // ================================================================ phase 1: Q_h = LayerNorm(x) Wq_h^T
-    const i32x4 rs_x = make_rsrc_words(p.x + ((size_t)b * p.Nq) * C, (unsigned)((size_t)p.Nq * C * 2));
+    const int bx = PER ? b % p.P : b;
+    const i32x4 rs_x = make_rsrc_words(p.x + ((size_t)bx * p.Nq) * C, (unsigned)((size_t)p.Nq * C * 2));
     const i32x4 rs_w = make_rsrc_words(p.wq, (unsigned)((size_t)C * C * 2));
     unsigned voff_x[4], voff_w[DB];
 #pragma unroll
@@ -425,16 +429,16 @@ constexpr int xattn_lds_bytes() {
     return ((NST * ST > AL * TILE) ? NST * ST : AL * TILE) + (EK ? TILE : 0) + 16 * KS * 6;
 }
 
-template <int D, int NST, bool EK, int OCC>
+template <int D, int NST, bool EK, int OCC, bool PER = false>
 int launch_xattn(XAttnArgs a, hipStream_t stream) {
     constexpr int LDS = xattn_lds_bytes<D, NST, EK>();
     static_assert(LDS * OCC <= 160 * 1024, "LDS budget at the requested occupancy");
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static std::atomic<unsigned long long> done{0};
-    if (const int rc = vd_reserve_lds({(const void*)&xattn_kernel<D, NST, EK, OCC>}, LDS, done, "vd_xattn_f16")) return rc;
+    if (const int rc = vd_reserve_lds({(const void*)&xattn_kernel<D, NST, EK, OCC, PER>}, LDS, done, "vd_xattn_f16")) return rc;
     a.nqb = (a.Nq + 127) / 128;
     a.xcd_map = ((a.B * a.nqb) & 7) == 0 ? 1 : 0;
-    hipLaunchKernelGGL((xattn_kernel<D, NST, EK, OCC>), dim3(a.nqb * a.B * a.H), dim3(256), LDS, stream, a);
+    hipLaunchKernelGGL((xattn_kernel<D, NST, EK, OCC, PER>), dim3(a.nqb * a.B * a.H), dim3(256), LDS, stream, a);
     return vd_check_launch("vd_xattn_f16");
 }
 
@@ -444,9 +448,9 @@ extern "C" int vd_xattn_supported(int H, int D) {
     return (D == 40 || D == 80 || D == 160) && H > 0 && ((H * D) % 64) == 0 ? 1 : 0;
 }
 
-extern "C" int vd_xattn_f16(const void* x, const void* wq, const void* bq, const float* colsum, float ln_eps, const void* k,
-                            const void* v, void* out, int B, int H, int Nq, int Nk, int D, int ldk, int ldv, int64_t sk,
-                            int64_t sv, float scale, hipStream_t stream) {
+static int xattn_entry(const void* x, const void* wq, const void* bq, const float* colsum, float ln_eps, const void* k, const void* v,
+                       void* out, int B, int H, int Nq, int Nk, int D, int ldk, int ldv, int64_t sk, int64_t sv, float scale, int P,
+                       hipStream_t stream) {
     VD_REQUIRE(x && wq && colsum && k && v && out, "vd_xattn_f16: null pointer");
     VD_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0, "vd_xattn_f16: empty problem B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk);
     VD_REQUIRE(vd_xattn_supported(H, D), "vd_xattn_f16: unsupported heads x head dim %d x %d (head dim 40 / 80 / 160, width a multiple of 64)", H, D);
@@ -464,7 +468,15 @@ extern "C" int vd_xattn_f16(const void* x, const void* wq, const void* bq, const
     a.H = H; a.Nq = Nq; a.Nk = Nk; a.C = C; a.ldk = ldk; a.ldv = ldv; a.sk = sk; a.sv = sv;
     a.scale_log2 = scale * 1.44269504088896340736f;
     a.eps = ln_eps;
-    a.nqb = 0; a.B = B; a.xcd_map = 0;
+    a.nqb = 0; a.B = B; a.xcd_map = 0; a.P = P;
+    if (P < B) {   // x shared by the B / P replicas of a sample
+        VD_REQUIRE(P > 0 && B % P == 0, "vd_xattn_rep_f16: the batch %d is not a multiple of the %d samples of x", B, P);
+        switch (D) {
+            case 40: return launch_xattn<40, 2, false, 3, true>(a, stream);
+            case 80: return launch_xattn<80, 2, false, 2, true>(a, stream);
+            default: return launch_xattn<160, 4, false, 1, true>(a, stream);
+        }
+    }
     // development switch VD_XATTN_VAR: 1 = early K/V tile 0 (measured neutral: 42.6 / 24.3 / 32.7 us vs 43.3 / 24.1 / 30.4 at the
     // 64x64 / 32x32 / 16x16 levels), 2 = head dim 40 with the old 3-stage, 2-blocks-per-CU pipeline (43.3 us vs 38.3 at 3 blocks:
     // what hides the chunk latency is a third resident block, not a deeper pipeline)
@@ -473,4 +485,17 @@ extern "C" int vd_xattn_f16(const void* x, const void* wq, const void* bq, const
         case 80: return launch_xattn<80, 2, false, 2>(a, stream);
         default: return launch_xattn<160, 4, false, 1>(a, stream);
     }
+}
+
+extern "C" int vd_xattn_f16(const void* x, const void* wq, const void* bq, const float* colsum, float ln_eps, const void* k,
+                            const void* v, void* out, int B, int H, int Nq, int Nk, int D, int ldk, int ldv, int64_t sk,
+                            int64_t sv, float scale, hipStream_t stream) {
+    return xattn_entry(x, wq, bq, colsum, ln_eps, k, v, out, B, H, Nq, Nk, D, ldk, ldv, sk, sv, scale, B, stream);
+}
+
+extern "C" int vd_xattn_rep_f16(const void* x, const void* wq, const void* bq, const float* colsum, float ln_eps, const void* k,
+                                const void* v, void* out, int B, int x_samples, int H, int Nq, int Nk, int D, int ldk, int ldv,
+                                int64_t sk, int64_t sv, float scale, hipStream_t stream) {
+    VD_REQUIRE(x_samples > 0 && x_samples <= B, "vd_xattn_rep_f16: x_samples %d outside 1 .. B = %d", x_samples, B);
+    return xattn_entry(x, wq, bq, colsum, ln_eps, k, v, out, B, H, Nq, Nk, D, ldk, ldv, sk, sv, scale, x_samples, stream);
 }

@@ -110,15 +110,21 @@ class CrossAttention(nn.Module, PackCache):
         return self._packed("q_ln", (self.to_q.weight, ln.weight, ln.bias),
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
 
-    def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False):
+    def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False, repeat=1):
         """ln_sums: row statistics of x for `ln` (from x's producer); out_sums: zeroed fp32 [rows, 2] the output projection
         accumulates the row statistics of ITS output into (for the LayerNorm in front of the next block part).
         defer_out: return the attention output `a` WITHOUT the output projection (the caller folds to_out + res into its next
         launch: ops.ff_chain); only honoured on the one-launch cross-attention path, else the projected tensor comes back as usual.
         x [B, N, C] -> to_out(attn) (+ res fused).  ln: the LayerNorm in front of the block's q (and self k / v)
         projections, folded into them -- x is then the un-normalised input.  qkv: the fused self-attention projection when
-        the caller has already computed it (SpatialTransformer's chained entry kernel)."""
+        the caller has already computed it (SpatialTransformer's chained entry kernel).
+        repeat > 1 (with a context; only with defer_out on the one-launch path, i.e. where vd_xattn_rep_f16 applies): x holds ONE
+        replica of a classifier-free-guidance batch, context / kv all of them; the result has repeat times the samples of x."""
         c = self.inner
+        if repeat > 1 and not (defer_out and (context is not None or kv is not None) and ln is not None and x.dim() == 3
+                               and x.is_contiguous() and ops.xattn_supported(self.heads, c // self.heads)):
+            raise ops.VdHipError("CrossAttention(repeat=%d): no cross-attention kernel with a batch period for this call "
+                                 "(width %d, %d heads); replicate the input in front" % (repeat, c, self.heads))
         if context is None and kv is None:
             if qkv is not None:
                 pass
@@ -134,7 +140,7 @@ class CrossAttention(nn.Module, PackCache):
             if ln is not None and x.dim() == 3 and x.is_contiguous() and ops.xattn_supported(self.heads, c // self.heads):
                 # LayerNorm + to_q + attention over the (short) context in ONE launch: q never exists in memory
                 w, b, cs = self._w_q_ln(ln)
-                a = ops.xattn(x, w, b, cs, ln.eps, kv[..., :c], kv[..., c:], self.heads, scale=self.scale)
+                a = ops.xattn(x, w, b, cs, ln.eps, kv[..., :c], kv[..., c:], self.heads, scale=self.scale, repeat=repeat)
                 if defer_out:
                     a._vd_deferred_out = True
                     return a
@@ -146,6 +152,14 @@ class CrossAttention(nn.Module, PackCache):
                 q = ops.linear(x, w, b, colsum=cs, ln_eps=ln.eps)
             a = ops.attention(q, kv[..., :c], kv[..., c:], self.heads, scale=self.scale)
         return self.to_out[0](a, res=res, row_sums=out_sums)
+
+
+def period_consumers(C, heads):
+    """Whether a transformer block of width C can run its self-attention once per sample of a guided batch: behind attn1 the
+    cross-attention (vd_xattn_rep_f16) and the chained tail with its first projection (vd_ff_chain_f16, VdFfChain.period_rows)
+    must both be there to read the shared activation through the batch period."""
+    return bool(hip_layers.LN_FOLD and heads > 0 and C % heads == 0 and ops.xattn_supported(heads, C // heads)
+                and ops.ff_geglu_supported(C) and ops.ff_chain_supported(C, "pre"))
 
 
 class BasicTransformerBlock(nn.Module):
@@ -161,11 +175,18 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = LayerNorm(dim)
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
-    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None):
+    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
-        SpatialTransformer.forward)."""
+        SpatialTransformer.forward).
+        repeat > 1: x (and post's res) hold ONE replica of a classifier-free-guidance batch, context / kv all of them.  Nothing
+        reads the context before attn2, so attn1 runs on the one replica; the launches that first meet per-replica data -- the
+        cross-attention and the chained tail -- read x / res through the batch period.  Only widths that have both kernels take
+        repeat > 1 (period_consumers; C = 320): any other call is an error, the caller replicates in front of the block.  The result
+        has repeat times the samples of x."""
+        if repeat > 1 and not period_consumers(x.shape[-1], self.attn2.heads):
+            raise ops.VdHipError("BasicTransformerBlock(repeat=%d): width %d has no consumers with a batch period" % (repeat, x.shape[-1]))
         if hip_layers.LN_FOLD:  # the three LayerNorms ride in the q/k/v, q and GEGLU projections (VD_EPI_LNFOLD)
             x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums)
             C = x.shape[-1]
@@ -173,10 +194,15 @@ class BasicTransformerBlock(nn.Module):
             if fops is not None and (ops.ff_chain_supported(C, "pre") or (post is not None and ops.ff_chain_supported(C, "post"))):
                 # 64x64 level: attn2.to_out + x -> norm3 -> feed-forward -> + x [-> proj_out -> + x_in] in ONE launch
                 w1p, b1p, w2, b2 = fops
+                if repeat > 1 and not (x.dim() == 3 and ops.ff_chain_period_ok(x.shape[1])):
+                    # (a 128-row tile of the chained tail would straddle two samples: replicate behind attn1)
+                    if post is not None:
+                        post = post[:3] + (ops.repeat_batch(post[3], repeat),) + post[4:]
+                    x, repeat = ops.repeat_batch(x, repeat), 1
                 kw = {}
                 xin = x
                 if ops.ff_chain_supported(C, "pre"):
-                    a = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, defer_out=True)
+                    a = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, defer_out=True, repeat=repeat)
                     if getattr(a, "_vd_deferred_out", False):
                         wo, bo = self.attn2.to_out[0]._w()
                         kw.update(a=a, wo=wo, bo=bo)
@@ -191,11 +217,15 @@ class BasicTransformerBlock(nn.Module):
                 if kw:
                     if folded and sync is not None:
                         sync()
+                    if repeat > 1:   # x (with a) and pres stay un-replicated: the kernel reads them through the batch period
+                        kw.update(repeat=repeat, stat_img_rows=x.shape[1])
                     out = ops.ff_chain(xin, w1p, b1p, w2, b2, self.norm3.eps, **kw)
                     return (out, True) if folded else out
                 return self.ff(xin, res=xin, ln=self.norm3)
             # norm3's statistics: accumulated by attn2's output projection where the feed-forward runs as separate GEMMs (the
             # one-launch feed-forward of the 64x64 level normalises in registers)
+            if repeat > 1:
+                raise ops.VdHipError("BasicTransformerBlock(repeat=%d): the chained tail does not take this feed-forward" % repeat)
             C = x.shape[-1]
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
@@ -227,11 +257,23 @@ class SpatialTransformer(nn.Module):
     def project_context(self, context):
         return self.transformer_blocks[0].attn2.project_context(context)
 
-    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None):
+    def shares_cfg_head(self):
+        """True when forward(repeat > 1) reads the shared activation through the batch period of the one-launch cross-attention
+        and of the chained tail (vd.run_unet hands a guided batch over un-replicated only then)."""
+        return period_consumers(self.proj_in.out_channels, self.transformer_blocks[0].attn2.heads)
+
+    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1):
         """Returns alpha * (proj_out(...) + bias) + res, res defaulting to x (the block's own skip).
         alpha/res implement VD's context mixing sum_i r_i * ST_i(x) without extra passes.
         sync: callable invoked right before the ONE launch that reads `res` (the last of the block): the caller runs the blocks
-        of several context types on forked streams and `res` is the previous type's output (vd.run_unet)."""
+        of several context types on forked streams and `res` is the previous type's output (vd.run_unet).
+        repeat > 1: x holds ONE replica of a classifier-free-guidance batch (vd.run_unet(repeat=...)), context / kv all of them;
+        the entry and the self-attention run once per sample and the output has repeat times the samples of x (the block's own
+        skip only: res is None)."""
+        assert repeat == 1 or res is None, "a shared input takes the block's own skip"
+        if repeat > 1 and not self.shares_cfg_head():
+            raise ops.VdHipError("SpatialTransformer(repeat=%d): width %d has no consumers with a batch period; replicate in front"
+                                 % (repeat, self.proj_in.out_channels))
         B, H, W, C = x.shape
         blk = self.transformer_blocks[0]
         inner = self.proj_in.out_channels
@@ -248,21 +290,26 @@ class SpatialTransformer(nn.Module):
             if pres.is_contiguous() and self.proj_out.out_channels == inner and self.proj_out.bias is not None:
                 wp, bp = self.proj_out._w()
                 post = (wp, bp, float(alpha), pres.view(B, H * W, C), H * W)
-            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync)
+            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat)
             if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the block's last launch
                 out = h[0]
                 st = ops.stats_of(out)
-                out = out.view(B, H, W, C)
+                out = out.view(repeat * B, H, W, C)
                 if st is not None:
                     out._vd_stats = st
                 return out
             if sync is not None:
                 sync()
-            return self.proj_out(h.view(B, H, W, -1), alpha=alpha, res=pres, want_stats=True)
+            if repeat > 1:
+                pres = ops.repeat_batch(pres, repeat)
+            return self.proj_out(h.view(repeat * B, H, W, -1), alpha=alpha, res=pres, want_stats=True)
         # norm1's row statistics ride on proj_in's epilogue (ops.gemm(row_sums=...)) instead of a vd_row_stats_f16 launch
         s1 = ops.rowsum_take(B * H * W, x.device) if hip_layers.LN_FOLD else None
         h = self.proj_in(self.norm(x, silu=False), row_sums=s1)
-        h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None))
+        h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
+                                       repeat=repeat)
         if sync is not None:
             sync()
-        return self.proj_out(h.view(B, H, W, -1), alpha=alpha, res=x if res is None else res, want_stats=True)
+        if repeat > 1:   # (proj_out's residual read has no batch period)
+            res = ops.repeat_batch(x, repeat)
+        return self.proj_out(h.view(repeat * B, H, W, -1), alpha=alpha, res=x if res is None else res, want_stats=True)

@@ -20,7 +20,7 @@ import torch
 from vd_hip import ops
 
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import kv_mark_stale, kv_refresh, kv_refreshable
+from .vd import capture_stream, kv_mark_stale, kv_refresh, kv_refreshable
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -500,7 +500,7 @@ class DDIMSampler(object):
     def _capture_step(self, body):
         try:
             g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
+            s = capture_stream()   # (never a side stream of the forked UNet branches)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 with torch.cuda.graph(g, stream=s):

@@ -40,6 +40,9 @@ class String_Reg_Buffer(nn.Module):
 
 
 CTX_FORK = os.environ.get("VD_CTX_FORK", "1") != "0"   # development switch: 0 = the context types of a block one after the other
+# run_unet(repeat > 1): the first context block of a step with ONE context type takes the un-replicated activation and runs its entry
+# and self-attention once per sample (SpatialTransformer.forward(repeat=...)); 0 = replicate in front of the block
+CFG_HEAD_SHARE = os.environ.get("VD_CFG_HEAD_SHARE", "1") != "0"
 # Round 6: the low-resolution levels of the UNet (rows per sample <= VD_BATCH_FORK_HW, default 256 = the 16x16 and 8x8 levels and the
 # middle block) as TWO forked branches of half the batch each.  Measured (profiles/HISTORY.md R6.8): image variation at CFG batch 16
 # +1.6 .. +2.5 % images/s (each half is the CFG-batch-8 problem the planner's rules were measured on, and the halves' latency-bound
@@ -57,25 +60,60 @@ def _side_streams(device, n, kind="ctx"):
     """Side streams of the forked branches, one set per (thread, device): the sampler's eager warm-up step and its captured
     step run on one thread and use the same streams, so the per-stream workspaces of vd_hip.ops (keyed by stream) are
     allocated once, outside any capture; two threads never put their branches -- and split-K slabs -- on one stream.
-    (torch hands out streams round-robin from a fixed pool: one another live thread forks onto is skipped.)"""
+    torch hands out streams round-robin from a fixed pool of 32 per device, so a new torch.cuda.Stream() can BE a stream this
+    process already uses: one another live thread forks onto, one of this thread's own side streams, or the stream the fork
+    starts from (the capture stream of torch.cuda.graph, or a sampler's).  A branch "forked" onto the caller's own stream waits for
+    and is joined through events of that same stream, which ends a stream capture in a crash of the runtime -- which streams meet
+    depends on how many streams the process has created before.  So the n streams handed out are distinct from each other, from
+    this thread's streams of the other kinds and from the CURRENT stream; a kept stream that is the current one is passed over
+    for this call (capture_stream() gives a sampler a stream that is none of them, so that does not happen to its captures).
+    Cost of passing over, accepted: the thread's list can grow by one stream per distinct current stream that was a kept one (at
+    most the 32 handles of the pool), and the replacement can be first used -- and its ops workspaces first allocated -- inside a
+    capture of a caller that captures on a stream of its own choosing; those workspaces then live in that graph's pool, as the
+    capture stream's own do."""
     me = threading.get_ident()
+    main = torch.cuda.current_stream(device).cuda_stream
     with _SIDE_LOCK:
-        lst = _SIDE.get((kind, device.index, me), [])
-        if len(lst) < n:
+        lst = _SIDE.setdefault((kind, device.index, me), [])
+        pick = [s for s in lst if s.cuda_stream != main][:n]
+        if len(pick) < n:
             alive = {t.ident for t in threading.enumerate()} | {me}
             for k in [k for k in _SIDE if k[2] not in alive]:
                 del _SIDE[k]
             _SIDE[(kind, device.index, me)] = lst
-            taken = {s.cuda_stream for k, l in _SIDE.items() if k[2] != me for s in l}
+            taken = {s.cuda_stream for k, l in _SIDE.items() if k[1] == device.index for s in l}   # other threads', and this thread's own
+            taken.add(main)
             for _ in range(64):
-                if len(lst) >= n:
+                if len(pick) >= n:
                     break
                 s = torch.cuda.Stream(device=device)
                 if s.cuda_stream not in taken:
+                    taken.add(s.cuda_stream)
                     lst.append(s)
-            if len(lst) < n:
-                raise RuntimeError("run_unet: no side stream left that no other thread forks onto")
-        return lst[:n]
+                    pick.append(s)
+            if len(pick) < n:
+                raise RuntimeError("run_unet: no side stream left that neither this thread nor another one already uses")
+        return pick
+
+
+def side_stream_handles(device=None):
+    """Raw handles of every side stream kept for forked branches (all threads): a stream a caller creates to capture forwards on
+    should be none of them, so that the captured step forks onto the streams its eager warm-up step used."""
+    idx = None if device is None else torch.device(device).index
+    with _SIDE_LOCK:
+        return {s.cuda_stream for k, l in _SIDE.items() if idx is None or k[1] == idx for s in l}
+
+
+def capture_stream(device=None):
+    """A stream to capture forwards on that is no kept side stream (torch's pool hands the same 32 streams out again and again): the
+    captured step then forks onto the very streams its eager warm-up step used."""
+    busy = side_stream_handles(device)
+    s = None
+    for _ in range(64):
+        s = torch.cuda.Stream(device=device)
+        if s.cuda_stream not in busy:
+            break
+    return s
 
 
 class _BranchOrder(object):
@@ -152,7 +190,9 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     repeat > 1: the batch the reference would feed is `x` replicated `repeat` times ([x; x] of classifier-free guidance,
     ddim.py:144-149) with identical timesteps per replica, while contexts / emb carry the full repeat * B rows.  The data
     blocks in front of the first context block see identical inputs in every replica, so they run once on B rows and the
-    result (and the skip tensors saved so far) is replicated where the contexts make the replicas diverge.
+    result (and the skip tensors saved so far) is replicated where the contexts make the replicas diverge.  With one context
+    type that is INSIDE the first context block, behind its self-attention (CFG_HEAD_SHARE): the block takes h un-replicated and
+    returns all repeat * B samples; with several types h is replicated in front of the block.
     emb_rows: {data block index: [Cout] fp16} complete first-conv bias vectors of the ResBlocks for the ONE timestep the whole
     batch shares (VD_v2_0.precompute_step_emb); emb_silu may then be None."""
     d_iter = iter(enumerate(data_net.data_blocks))
@@ -186,9 +226,13 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None):
-        """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike."""
+    def run_context(h, modules, specs, rs, sl=None, repeat=1):
+        """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
+        repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them."""
         single = len(modules) == 1
+        if repeat > 1:
+            assert single and sl is None
+            return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat)
         kvs = [context_kv(m, sp) for m, sp in zip(modules, specs)]
         if sl is not None:
             kvs = [None if kv is None else kv[sl[0]:sl[1]] for kv in kvs]
@@ -245,6 +289,13 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
         data_net.__dict__["_vd_rowsum_need"] = arena.need
 
 
+def _shares_cfg_head(module):
+    """Whether the context block `module` can take a guided batch un-replicated: its consumers behind the self-attention are the
+    kernels with a batch period (width 320: vd_xattn_rep_f16 and vd_ff_chain_f16).  Every other block gets the replicas in front."""
+    st = module[0] if isinstance(module, (nn.Sequential, list, tuple)) else module
+    return bool(getattr(st, "shares_cfg_head", lambda: False)())
+
+
 def _fork_region(steps, hw0, thr):
     """[a, b) of `steps`: from the Downsample that brings the rows per sample to <= thr up to (not including) the Upsample that
     leaves that range again, or None.  The region must keep its skip tensors to itself (as many loads as saves, never below)."""
@@ -290,11 +341,16 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                     h = blk(h, rows(emb_silu), None, skip=skip, emb_out=rows(eo), emb_bias=emb_rows.get(di))
                 skip = None
             elif st[0] == "c":
+                share = 1
                 if state["shared"]:  # the replicas diverge here
                     rep = lambda t: ops.repeat_batch(t, repeat)   # per-channel statistics of the tensors travel along
-                    h, hs[:] = rep(h), [rep(t) for t in hs]
+                    hs[:] = [rep(t) for t in hs]
+                    if CFG_HEAD_SHARE and len(st[1]) == 1 and sl is None and h.dim() == 4 and _shares_cfg_head(st[1][0]):
+                        share = repeat   # ... inside the block, behind its self-attention: h goes in un-replicated
+                    else:
+                        h = rep(h)
                     state["shared"] = False
-                h = run_context(h, st[1], st[2], st[3], sl)
+                h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
             elif st[0] == "save":
                 hs.append(h)
             elif st[0] == "load":

@@ -44,7 +44,7 @@ class VdFfChain(ctypes.Structure):
                 ("res", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_stats", ctypes.c_void_p),
                 ("stat_sums", ctypes.c_void_p), ("stat_img_rows", ctypes.c_int64),
                 ("M", ctypes.c_int64), ("C", ctypes.c_int32), ("ln_eps", ctypes.c_float), ("alpha", ctypes.c_float),
-                ("reserved", ctypes.c_int32)]
+                ("period_rows", ctypes.c_int32)]
 
 
 # name -> (restype, argtypes); mirrors include/vd_hip.h one to one (checked by
@@ -97,6 +97,7 @@ PROTOTYPES = {
     "vd_attention_f16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P]),
     "vd_xattn_f16": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, _P]),
     "vd_xattn_supported": (_I, [_I, _I]),
+    "vd_xattn_rep_f16": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, _P]),
     "vd_softmax_rows_f32_f16": (_I, [_P, _P, _L, _I, _P]),
     "vd_softmax_rows_f32_f32": (_I, [_P, _P, _L, _I, _F, _P]),
     "vd_timestep_embedding_f16": (_I, [_P, _P, _I, _I, _F, _P]),

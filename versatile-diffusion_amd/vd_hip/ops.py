@@ -641,29 +641,44 @@ def ff_chain_supported(C, which="both"):
     return bool(lib().vd_ff_chain_supported(int(C)))
 
 
+def ff_chain_period_ok(hw):
+    """Whether vd_ff_chain_f16 takes residual operands shared by the replicas of a sample (`repeat`): whole images of hw rows that
+    no 128-row tile straddles."""
+    return int(hw) > 0 and int(hw) % 128 == 0
+
+
 def ff_chain(x, w1_packed, b1_packed, w2, b2, ln_eps, *, a=None, wo=None, bo=None, wp=None, bp=None, res=None, alpha=1.0,
-             want_stats=False, stat_img_rows=0):
+             want_stats=False, stat_img_rows=0, repeat=1):
     """x1 = a wo^T + bo + x (with a);  y = x1 + FF(LayerNorm(x1));  out = alpha (y wp^T + bp) + res (with wp) in one launch
     (vd_ff_chain_f16, C = 320).  Returns out (or y); with want_stats and wp the per-channel statistics of the stored output
-    ride on it as `_vd_stats` (partials of 128 rows)."""
+    ride on it as `_vd_stats` (partials of 128 rows).
+    repeat > 1: the residual operands -- x when `a` is given, and res -- hold the rows of ONE replica of a classifier-free-guidance
+    batch (M / repeat rows, images of stat_img_rows rows); a and the output have all M rows (VdFfChain.period_rows)."""
     for t, n in ((x, "x"), (w1_packed, "w1"), (b1_packed, "b1"), (w2, "w2"), (b2, "b2"), (a, "a"), (wo, "wo"), (bo, "bo"), (wp, "wp"),
                  (bp, "bp"), (res, "res")):
         _req(t, n)
     C = x.shape[-1]
-    M = x.numel() // C
+    repeat = int(repeat)
+    full = a if (a is not None and repeat > 1) else x   # the tensor that has the rows (and the shape) of the output
+    M = full.numel() // C
+    period = M // repeat if repeat > 1 else 0
+    if repeat > 1 and (M % repeat or (a is None and wp is None)):
+        raise VdHipError("ff_chain: repeat=%d does not divide the %d rows, or no operand is shared" % (repeat, M))
     if tuple(w1_packed.shape) != (8 * C, C) or tuple(w2.shape) != (C, 4 * C):
         raise VdHipError("ff_chain: feed-forward operand shapes do not match C=%d" % C)
-    if a is not None and (a.shape != x.shape or tuple(wo.shape) != (C, C) or bo is None):
+    if a is not None and (x.numel() * (repeat if repeat > 1 else 1) != a.numel() or a.shape[-1] != C or tuple(wo.shape) != (C, C) or bo is None):
         raise VdHipError("ff_chain: first projection operands do not match x")
-    if wp is not None and (tuple(wp.shape) != (C, C) or bp is None or res is None or res.numel() != x.numel()):
+    if wp is not None and (tuple(wp.shape) != (C, C) or bp is None or res is None or res.numel() * (repeat if repeat > 1 else 1) != M * C):
         raise VdHipError("ff_chain: last projection operands do not match x")
     d = VdFfChain()
     d.x, d.w1_packed, d.b1_packed, d.w2, d.b2 = x.data_ptr(), w1_packed.data_ptr(), b1_packed.data_ptr(), w2.data_ptr(), b2.data_ptr()
-    out = torch.empty_like(x)
+    out = torch.empty_like(full)
+    if period:
+        d.period_rows, d.stat_img_rows = period, int(stat_img_rows)
     d.out, d.M, d.C, d.ln_eps, d.alpha = out.data_ptr(), int(M), int(C), float(ln_eps), float(alpha)
     scratch = None
     if a is not None:
-        scratch = torch.empty_like(x)
+        scratch = torch.empty_like(full)
         d.a, d.wo, d.bo, d.x1_scratch = a.data_ptr(), wo.data_ptr(), bo.data_ptr(), scratch.data_ptr()
     stats = None
     if wp is not None:
@@ -892,10 +907,12 @@ def xattn_supported(heads, D):
     return XATTN_FUSED and bool(lib().vd_xattn_supported(int(heads), int(D)))
 
 
-def xattn(x, wq, bq, colsum, ln_eps, k, v, heads, *, scale=None):
+def xattn(x, wq, bq, colsum, ln_eps, k, v, heads, *, scale=None, repeat=1):
     """softmax((LayerNorm(x) wq_h^T) k_h^T * scale) v_h per head in one launch (vd_xattn_f16).  x [B, Nq, C] contiguous;
     wq / bq / colsum: the LayerNorm-folded query projection (hip_layers.fold_layernorm); k, v [B, Nk, *] last-dim views
-    of the pre-projected context.  Returns [B, Nq, C]."""
+    of the pre-projected context.  Returns [B, Nq, C].
+    repeat > 1: x is [B / repeat, Nq, C], shared by the replicas of a classifier-free-guidance batch -- sample b of k / v and of
+    the result reads sample b % (B / repeat) of it (vd_xattn_rep_f16)."""
     for t, n in ((x, "x"), (wq, "wq")):
         _req(t, n)
     _req(colsum, "colsum", torch.float32)
@@ -904,10 +921,11 @@ def xattn(x, wq, bq, colsum, ln_eps, k, v, heads, *, scale=None):
     for t, n in ((k, "k"), (v, "v")):
         if not t.is_cuda or t.dtype != torch.float16 or t.stride(-1) != 1 or t.dim() != 3:
             raise VdHipError("%s must be a 3-d fp16 GPU tensor with unit inner stride" % n)
-    B, Nq, C = x.shape
+    P, Nq, C = x.shape
+    B = P * int(repeat)
     Nk = k.shape[1]
     D = C // heads
-    if tuple(wq.shape) != (C, C) or colsum.numel() != C or k.shape[0] != B or v.shape[1] != Nk or k.shape[2] != C or v.shape[2] != C:
+    if tuple(wq.shape) != (C, C) or colsum.numel() != C or k.shape[0] != B or v.shape[0] != B or v.shape[1] != Nk or k.shape[2] != C or v.shape[2] != C:
         raise VdHipError("xattn: operand shapes do not match B=%d C=%d" % (B, C))
     if scale is None:
         scale = D ** -0.5
@@ -915,9 +933,14 @@ def xattn(x, wq, bq, colsum, ln_eps, k, v, heads, *, scale=None):
     flops = 2.0 * B * Nq * C * C + 4.0 * B * Nq * Nk * C
     with _Timed(("xattn_kernel<%d>" % D) + ((" Nq=%d Nk=%d B=%d" % (Nq, Nk, B)) if PROFILE_SHAPES else ""), flops,
                 2.0 * (2 * B * Nq * C + C * C + 2 * B * Nk * C)):
-        _check(lib().vd_xattn_f16(_ptr(x), _ptr(wq), _ptr(bq) if bq is not None else None, _ptr(colsum), float(ln_eps),
-                                  _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, k.stride(1), v.stride(1), k.stride(0),
-                                  v.stride(0), float(scale), _stream()))
+        if P == B:
+            _check(lib().vd_xattn_f16(_ptr(x), _ptr(wq), _ptr(bq) if bq is not None else None, _ptr(colsum), float(ln_eps),
+                                      _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, k.stride(1), v.stride(1), k.stride(0),
+                                      v.stride(0), float(scale), _stream()))
+        else:
+            _check(lib().vd_xattn_rep_f16(_ptr(x), _ptr(wq), _ptr(bq) if bq is not None else None, _ptr(colsum), float(ln_eps),
+                                          _ptr(k), _ptr(v), _ptr(out), B, P, heads, Nq, Nk, D, k.stride(1), v.stride(1),
+                                          k.stride(0), v.stride(0), float(scale), _stream()))
     return out
 
 
