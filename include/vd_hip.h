@@ -209,6 +209,16 @@ int vd_conv3x3_wstream_supported(const VdGemmDesc* desc);
  * fused epilogue and the GroupNorm statistics run in the kernel): no workspace, no reduce launch. */
 int vd_conv3x3_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 int vd_gemm_wstream_plan(const VdGemmDesc* desc, int* nsplit);
+/* vd_gemm_wstream_cat_f16: vd_gemm_wstream_f16 over a CONCATENATED K axis, y = [a0 | a1] W^T: chunk c of the activation tile
+ * comes from desc->a0 (lda0) while c < c0 / 64 and from desc->a1 (lda1) after that (c0 % 64 == 0, c1 % 64 == 0, K = c0 + c1; a1 may
+ * be null: one source); w_stream is ONE fragment-order stream over K (pack_linear_weight_stream of the concatenated matrix).  A
+ * block takes up to 34 chunks, so K = 6400 on 2048 rows runs as 3 splits (240 blocks) -- FeedForward.net[2] with
+ * SpatialTransformer.proj_out folded in (A = [h | x2], vd_hip/pack.py: pack_ff_proj_fold).  The reduce runs desc's epilogue (bias,
+ * alpha, residual) and emits desc->out_stats in partials of 64 rows when asked.  _supported / _plan as for vd_gemm_wstream_f16;
+ * the answers of those three entries are unchanged. */
+int vd_gemm_wstream_cat_supported(const VdGemmDesc* desc);
+int vd_gemm_wstream_cat_plan(const VdGemmDesc* desc, int* nsplit);
+int vd_gemm_wstream_cat_f16(const VdGemmDesc* desc, const void* w_stream, hipStream_t stream);
 /* Development hook: kernel instance (0 = default) and the grid size the split over chunks aims for (256). Process-global. */
 int vd_conv3x3_wstream_set_variant(int variant, int target_blocks);
 /* The 3x3 / stride 1 / pad 1 convolution behind a nearest-2x upsample (VdGemmDesc.ups = 1: Upsample.conv of the UNet and of the

@@ -262,8 +262,101 @@ extern "C" int vd_gemm_wstream_f16(const VdGemmDesc* dp, const void* w_stream, h
     w.cps = (w.nchunks + nsplit - 1) / nsplit;
     nsplit = (w.nchunks + w.cps - 1) / w.cps;
     w.nsplit = nsplit;
-    hipLaunchKernelGGL(gemm_wstream_kernel, dim3(tiles * nsplit), dim3(256), 2 * GW_TILE, stream, w);
+    hipLaunchKernelGGL((gemm_wstream_kernel<GW_MAXC, GwArgs>), dim3(tiles * nsplit), dim3(256), 2 * GW_TILE, stream, w);
     const int lrc = vd_check_launch("vd_gemm_wstream_f16");
+    if (lrc != VD_OK) return lrc;
+    return vd_gemm_launch_reduce(&a, nsplit, stream);
+}
+
+
+// ---- the same kernel over a concatenated K axis: A = [a0 | a1], up to GW_MAXC_LONG chunks per block -----------------------
+// (FeedForward.net[2] with SpatialTransformer.proj_out folded in: A = [h | x2], K = 4C + C, hip_layers.FFProjFold.)  Entries of
+// their own: what vd_gemm_wstream_supported / _plan / _f16 answer and launch is pinned and stays as it is.
+namespace {
+const char* gwc_reject(const VdGemmDesc& d) {
+    if (d.ksize > 1 || d.stride > 1 || d.pad != 0 || d.ups != 0 || d.batch != 1) return "a plain unbatched GEMM";
+    const int c1 = d.a1 != nullptr ? d.c1 : 0;
+    const int c0 = d.c0 > 0 ? d.c0 : d.K - c1;
+    if (d.M % 128 != 0 || d.N % 256 != 0 || c0 <= 0 || c0 % 64 != 0 || c1 % 64 != 0 || c0 + c1 != d.K) return "M % 128 == 0, N % 256 == 0, c0 % 64 == 0, c1 % 64 == 0, K == c0 + c1";
+    if (d.K / 64 > VD_MAX_SPLIT_K * GW_MAXC_LONG) return "K <= 69632 (the unrolled chunk sequence times the largest split)";
+    if ((d.flags & (VD_EPI_LNFOLD | VD_EPI_OUT_F32 | VD_EPI_BIAS_ALONG_M)) || d.act == VD_ACT_GEGLU) return "a plain fp16 epilogue";
+    return nullptr;
+}
+// as gw_split, with the long chunk sequence as the bound: (2048, 1280, 6400) -> 3 splits of 34 chunks, 240 blocks
+int gwc_split(const VdGemmDesc& d, int tiles, int nchunks) {
+    const int target = 256;
+    int nsplit = d.split_k > 0 ? d.split_k : (target + tiles / 2) / tiles;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit > nchunks) nsplit = nchunks;
+    if (nsplit > VD_MAX_SPLIT_K) nsplit = VD_MAX_SPLIT_K;
+    if ((nchunks + nsplit - 1) / nsplit > GW_MAXC_LONG) nsplit = (nchunks + GW_MAXC_LONG - 1) / GW_MAXC_LONG;
+    return nsplit;
+}
+}  // namespace
+
+extern "C" int vd_gemm_wstream_cat_supported(const VdGemmDesc* dp) {
+    if (dp == nullptr) return 0;
+    VdGemmDesc d = *dp;
+    if (d.batch <= 0) d.batch = 1;
+    return gwc_reject(d) == nullptr ? 1 : 0;
+}
+
+// Split factor vd_gemm_wstream_cat_f16 will use for `desc` (size the workspace with it: VdGemmDesc.split_k).
+extern "C" int vd_gemm_wstream_cat_plan(const VdGemmDesc* dp, int* nsplit) {
+    VD_REQUIRE(dp != nullptr && nsplit != nullptr, "vd_gemm_wstream_cat_plan: null argument");
+    VD_REQUIRE(dp->M >= 128 && dp->N >= 256 && dp->K >= 64, "vd_gemm_wstream_cat_plan: M=%d N=%d K=%d below one tile", dp->M, dp->N, dp->K);
+    const int nchunks = dp->K / 64;
+    const int ns = gwc_split(*dp, (dp->M / 128) * (dp->N / 256), nchunks);
+    const int cps = (nchunks + ns - 1) / ns;
+    *nsplit = (nchunks + cps - 1) / cps;
+    return VD_OK;
+}
+
+extern "C" int vd_gemm_wstream_cat_f16(const VdGemmDesc* dp, const void* w_stream, hipStream_t stream) {
+    VD_REQUIRE(dp != nullptr && w_stream != nullptr, "vd_gemm_wstream_cat_f16: null argument");
+    VD_REQUIRE(dp->stat_sums == nullptr, "vd_gemm_wstream_cat_f16: stat_sums is taken by vd_gemm_f16 / vd_ff_chain_f16 only");
+    VdGemmDesc tmp = *dp;
+    tmp.w = w_stream;          // the K-contiguous weights are not read on this path
+    tmp.out_stats = nullptr;   // (validated below, not by the planner of the other kernels)
+    GemmArgs a;
+    const int rc = vd_gemm_normalise(&tmp, &a);
+    if (rc != VD_OK) return rc;
+    VdGemmDesc& d = a.d;
+    const char* why = gwc_reject(d);
+    VD_REQUIRE(why == nullptr, "vd_gemm_wstream_cat_f16 takes %s", why ? why : "");
+    VD_REQUIRE(d.ws != nullptr, "vd_gemm_wstream_cat_f16: needs the split-K workspace (vd_gemm_workspace_bytes)");
+    VD_REQUIRE(((size_t)w_stream & 15) == 0 && d.lda0 % 8 == 0 && d.lda1 % 8 == 0 && d.lda0 >= d.c0 && d.lda1 >= d.c1,
+               "vd_gemm_wstream_cat_f16: w_stream must be 16-byte aligned, lda0 / lda1 multiples of 8 that cover c0 / c1");
+    d.out_stats = dp->out_stats;
+    d.sync = nullptr;
+    if (d.out_stats != nullptr)
+        VD_REQUIRE(d.N % 8 == 0 && d.ldc % 8 == 0 && (!(d.flags & VD_EPI_RESIDUAL) || d.ldr % 8 == 0) && ((size_t)d.out_stats & 7) == 0 && d.M % 64 == 0,
+                   "vd_gemm_wstream_cat_f16: out_stats needs 16-byte row segments");
+    a.stat_rows = d.out_stats ? 64 : 0;
+    GwCatArgs w;
+    w.a = reinterpret_cast<const f16*>(d.a0); w.wp = reinterpret_cast<const uint4*>(w_stream); w.ws = d.ws;
+    w.lda = d.lda0; w.M = d.M; w.N = d.N;
+    w.nchunks = d.K / 64;
+    w.tiles_m = d.M / 128; w.tiles_n = d.N / 256;
+    w.a_bytes = a.a0_bytes;
+    w.c0_chunks = d.c0 / 64;
+    if (d.a1 != nullptr && d.c1 > 0) {
+        w.a1 = reinterpret_cast<const f16*>(d.a1); w.lda1 = d.lda1; w.a1_bytes = a.a1_bytes;
+    } else {   // one source: no chunk reaches the second descriptor (c0_chunks == nchunks)
+        w.a1 = w.a; w.lda1 = w.lda; w.a1_bytes = 0;
+    }
+    const int tiles = w.tiles_m * w.tiles_n;
+    int nsplit = gwc_split(d, tiles, w.nchunks);
+    VD_REQUIRE(nsplit <= VD_MAX_SPLIT_K, "vd_gemm_wstream_cat_f16: K = %d needs more than %d splits", d.K, VD_MAX_SPLIT_K);
+    w.cps = (w.nchunks + nsplit - 1) / nsplit;
+    nsplit = (w.nchunks + w.cps - 1) / w.cps;
+    w.nsplit = nsplit;
+    VD_REQUIRE(w.cps <= GW_MAXC_LONG, "vd_gemm_wstream_cat_f16: %d chunks per block exceed the unrolled sequence", w.cps);
+    if (w.cps <= GW_MAXC)
+        hipLaunchKernelGGL((gemm_wstream_kernel<GW_MAXC, GwCatArgs>), dim3(tiles * nsplit), dim3(256), 2 * GW_TILE, stream, w);
+    else
+        hipLaunchKernelGGL((gemm_wstream_kernel<GW_MAXC_LONG, GwCatArgs>), dim3(tiles * nsplit), dim3(256), 2 * GW_TILE, stream, w);
+    const int lrc = vd_check_launch("vd_gemm_wstream_cat_f16");
     if (lrc != VD_OK) return lrc;
     return vd_gemm_launch_reduce(&a, nsplit, stream);
 }

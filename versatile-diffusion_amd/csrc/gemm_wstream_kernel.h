@@ -22,9 +22,17 @@ struct GwArgs {
     int tiles_m, tiles_n, nsplit;
     unsigned a_bytes;
 };
+// ... with the second activation source of the concatenated entry (vd_gemm_wstream_cat_f16): chunks c >= c0_chunks of the K axis
+// come from a1.  (A struct of its own: the kernel arguments of the single-source instance stay what they were.)
+struct GwCatArgs : GwArgs {
+    const f16* a1;
+    int lda1, c0_chunks;
+    unsigned a1_bytes;
+};
 
 constexpr int GW_TILE = 128 * 128;   // bytes of one activation tile [128 rows][64 halfs]
 constexpr int GW_MAXC = 32;          // chunks per block (the chunk sequence is unrolled)
+constexpr int GW_MAXC_LONG = 34;     // ... of the long instance: K = 6400 (A = [h | x2], 5 x 1280) as 3 splits -- 240 blocks, one round
 
 template <int LO, int HI, class F>
 __device__ __forceinline__ void gw_static_for(F&& f) {
@@ -34,7 +42,11 @@ __device__ __forceinline__ void gw_static_for(F&& f) {
     }
 }
 
-__global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
+// MAXC: length of the unrolled chunk sequence.  P = GwCatArgs: the K axis is the concatenation of two activation matrices; the
+// weights stay ONE fragment-order stream over the concatenated K.
+template <int MAXC, class P>
+__global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const P p) {
+    constexpr bool CAT = std::is_same<P, GwCatArgs>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -72,10 +84,32 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
         const int row = m0 + r;
         avoff[j] = row < p.M ? (unsigned)((row * p.lda + (((lane & 7) ^ lds_swz<64>(r)) << 3)) * 2) : OOB_OFFSET;
     }
-    auto issue_a = [&](int c, int buf) {
+    // second source: its own descriptor and row offsets (another leading dimension); which of the two a chunk reads is decided
+    // per chunk on wave-uniform values -- descriptor and column offset in scalar registers
+    i32x4 rs_a1 = rs_a;
+    unsigned avoff1[4];
+    if constexpr (CAT) {
+        rs_a1 = make_rsrc_words(p.a1, p.a1_bytes);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            dma16(rs_a, lds0 + (unsigned)(buf * GW_TILE + (j * 4 + wave_s) * 1024), avoff[j], (unsigned)(c * 128));
+        for (int j = 0; j < 4; ++j) {
+            const int r = (j * 4 + wave) * 8 + (lane >> 3);
+            const int row = m0 + r;
+            avoff1[j] = row < p.M ? (unsigned)((row * p.lda1 + (((lane & 7) ^ lds_swz<64>(r)) << 3)) * 2) : OOB_OFFSET;
+        }
+    }
+    auto issue_a = [&](int c, int buf) {
+        if constexpr (CAT) {
+            const bool second = c >= p.c0_chunks;
+            const i32x4 rs = second ? rs_a1 : rs_a;
+            const unsigned soff = (unsigned)((second ? c - p.c0_chunks : c) * 128);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                dma16(rs, lds0 + (unsigned)(buf * GW_TILE + (j * 4 + wave_s) * 1024), second ? avoff1[j] : avoff[j], soff);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                dma16(rs_a, lds0 + (unsigned)(buf * GW_TILE + (j * 4 + wave_s) * 1024), avoff[j], (unsigned)(c * 128));
+        }
     };
 
     // ---- weight stream of this wave: two n tiles, 4 fragments (1 KiB each) per chunk and tile, chunks contiguous
@@ -116,9 +150,11 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
         const int c = c_begin + lc;
         // this chunk's activation tile (requested during the previous chunk, in front of the 8 weight loads of chunk c + 1) and
         // its weights (requested two chunks ago) have landed for this wave ... for every wave; every wave has left chunk c - 1,
-        // whose buffer the DMA below refills.  The last chunk a block can have has no weight loads behind its tile (chunk
-        // GW_MAXC + 1 does not exist, see below), so its tile is the newest request in flight: a count of 8 would not cover it
-        wait_vm<(lc + 1 < GW_MAXC ? 8 : 0)>();
+        // whose buffer the DMA below refills.  Requests in flight here, oldest first: W(lc) [8, from chunk lc - 2 or the
+        // prologue], A(lc) [4] and W(lc + 1) [8] (both from chunk lc - 1, the tile first): a count of 8 retires all but W(lc + 1).
+        // Chunk MAXC - 2 is the first that requests no weights (chunk MAXC does not exist, see below), so at chunk MAXC - 1 --
+        // and only there, whatever MAXC is -- the tile is the newest request in flight: a count of 8 would not cover it
+        wait_vm<(lc + 1 < MAXC ? 8 : 0)>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (lc + 1 < ncl) issue_a(c + 1, par ^ 1);
@@ -140,15 +176,15 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const GwArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             // issued whether or not chunk c + 2 is this block's (clamped): every chunk adds exactly 8 weight loads behind its
             // DMA pieces -- except where no block has a chunk lc + 2, which the wait of chunk lc + 1 above accounts for
-            if constexpr (lc + 2 < GW_MAXC) load_w(pt, kt, c + 2);
+            if constexpr (lc + 2 < MAXC) load_w(pt, kt, c + 2);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
-    // No loop: the chunks of a block (at most GW_MAXC, the launcher splits K accordingly) are unrolled behind forward guards.
+    // No loop: the chunks of a block (at most MAXC, the launcher splits K accordingly) are unrolled behind forward guards.
     // With a back edge hipcc cannot count the weight loads that are in flight ACROSS iterations and puts s_waitcnt vmcnt(0) in
     // front of the first MFMA of every iteration -- the ring drained once per trip (conv3x3_wstream_kernel pays that once per
     // 36-k-step chunk; here it would be every second 4-k-step chunk).
-    gw_static_for<0, GW_MAXC>([&](auto lt) {
+    gw_static_for<0, MAXC>([&](auto lt) {
         constexpr int lc = decltype(lt)::value;
         if (lc < ncl) chunk(lt);
     });

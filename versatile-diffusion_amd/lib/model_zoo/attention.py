@@ -60,10 +60,14 @@ class FeedForward(nn.Module):
         w2, b2 = out._w()
         return wp, bp, w2, b2
 
-    def forward(self, x, res=None, ln=None, ln_sums=None):
+    def forward(self, x, res=None, ln=None, ln_sums=None, post=None, sync=None):
         """ln: the LayerNorm in front (folded); ln_sums: row statistics of x from its producer (ops.gemm(row_sums=...)).  Where the library has the one-launch kernel for this width (C = 320: the
         64x64 level, whose [M, 4C] GEGLU intermediate is 84 MB) LayerNorm, both projections, the gating and the residual
-        run in vd_ff_geglu_f16; elsewhere GEGLU GEMM -> output GEMM."""
+        run in vd_ff_geglu_f16; elsewhere GEGLU GEMM -> output GEMM.
+        post = (proj_out, alpha, pres [.., C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be folded into
+        the output GEMM -- one launch over [h | res] with the pre-multiplied weights (Linear._w_proj_fold) instead of two, the
+        feed-forward's own output never stored.  Returns (proj_out's output, True) when it was, else the feed-forward's output
+        as without post (the caller runs proj_out).  sync: called right before the folded launch (the one that reads pres)."""
         C = x.shape[-1]
         proj, out = self.net[0].proj, self.net[2]
         if (ln is not None and res is not None and out.bias is not None and proj.bias is not None and proj.in_features == C
@@ -71,7 +75,22 @@ class FeedForward(nn.Module):
             wp, bp, _ = self.net[0].folded(ln)
             w2, b2 = out._w()
             return ops.ff_geglu(x, wp, bp, w2, b2, res, ln.eps)
-        return out(self.net[0](x, ln=ln, ln_sums=ln_sums), res=res)
+        h = self.net[0](x, ln=ln, ln_sums=ln_sums)
+        if (post is not None and res is not None and out.proj_fold_ok(post[0]) and res.shape[-1] == out.out_features
+                and h.is_contiguous() and res.is_contiguous() and post[2].is_contiguous()):
+            pconv, alpha, pres, hw = post
+            w_cat, bm = out._w_proj_fold(pconv)
+            m, n = h.numel() // h.shape[-1], out.out_features
+            kw = {}
+            # the same shapes Linear.forward hands to the weight-streaming kernel (16x16 / 8x8 levels), K now 5C
+            if ops.GEMM_WSTREAM and out.in_features >= 2048 and n % 256 == 0 and m % 128 == 0 and m <= 4096:
+                kw["w_stream_cat"] = out._w_proj_fold_stream(pconv)
+            if sync is not None:
+                sync()
+            y = ops.gemm(h.view(m, -1), w_cat, a1=res.view(m, n), bias=bm, alpha=float(alpha), res=pres.view(m, n), want_stats=True,
+                         stat_img_rows=int(hw), **kw)
+            return y, True
+        return out(h, res=res)
 
 
 class CrossAttention(nn.Module, PackCache):
@@ -175,11 +194,13 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = LayerNorm(dim)
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
-    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1):
+    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
         SpatialTransformer.forward).
+        ff_post = (proj_out, alpha, res, stat_img_rows): the same request where the feed-forward runs as separate GEMMs (widths 640 /
+        1280): proj_out is folded into the feed-forward's output GEMM by pre-multiplied weights (FeedForward.forward(post=...)).
         repeat > 1: x (and post's res) hold ONE replica of a classifier-free-guidance batch, context / kv all of them.  Nothing
         reads the context before attn2, so attn1 runs on the one replica; the launches that first meet per-replica data -- the
         cross-attention and the chained tail -- read x / res through the batch period.  Only widths that have both kernels take
@@ -229,7 +250,7 @@ class BasicTransformerBlock(nn.Module):
             C = x.shape[-1]
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
-            return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None))
+            return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None), post=ff_post, sync=sync)
         x = self.attn1(self.norm1(x), res=x)
         x = self.attn2(self.norm2(x), context=context, res=x, kv=kv)
         x = self.ff(self.norm3(x), res=x)
@@ -306,8 +327,20 @@ class SpatialTransformer(nn.Module):
         # norm1's row statistics ride on proj_in's epilogue (ops.gemm(row_sums=...)) instead of a vd_row_stats_f16 launch
         s1 = ops.rowsum_take(B * H * W, x.device) if hip_layers.LN_FOLD else None
         h = self.proj_in(self.norm(x, silu=False), row_sums=s1)
+        ff_post = None
+        if hip_layers.FF_PROJ_FOLD and hip_layers.LN_FOLD and repeat == 1 and self.proj_out.out_channels == inner:
+            pres = x if res is None else res
+            if pres.is_contiguous():   # proj_out rides in the feed-forward's output GEMM: that launch now is the one that reads res
+                ff_post = (self.proj_out, float(alpha), pres, H * W)
         h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
-                                       repeat=repeat)
+                                       repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None)
+        if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the feed-forward's output GEMM
+            out = h[0]
+            st = ops.stats_of(out)
+            out = out.view(B, H, W, C)
+            if st is not None:
+                out._vd_stats = st
+            return out
         if sync is not None:
             sync()
         if repeat > 1:   # (proj_out's residual read has no batch period)

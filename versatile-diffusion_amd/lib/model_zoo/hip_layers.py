@@ -15,6 +15,11 @@ from vd_hip import ops, pack
 
 # development switch: VD_LN_FOLD=0 runs every LayerNorm as its own kernel (A/B runs of the fold)
 LN_FOLD = os.environ.get("VD_LN_FOLD", "1") != "0"
+# SpatialTransformer.proj_out folded into the feed-forward's output projection where the two run as separate GEMMs (widths 640 /
+# 1280): out = alpha ([h | x2] [Wp W2 | Wp]^T + Wp b2 + bp) + r, one launch with K = 5C instead of K = 4C and K = C, and y = x2 +
+# h W2^T + b2 is neither written nor read.  Exact algebra with one added weight rounding (Wp W2), so not bit-identical to the
+# two launches.  VD_FF_PROJ_FOLD=0: the two launches everywhere
+FF_PROJ_FOLD = os.environ.get("VD_FF_PROJ_FOLD", "1") != "0"
 
 
 def _ver(t):
@@ -131,6 +136,28 @@ class Linear(nn.Linear, PackCache):
     def _w_stream(self):
         """The weight in MFMA-fragment order for vd_gemm_wstream_f16 (long-K projections applied to few rows)."""
         return self._packed("w_stream", (self.weight,), lambda: pack.pack_linear_weight_stream(_h(self.weight)))
+
+    def _w_proj_fold(self, proj):
+        """This layer followed by the 1x1 convolution `proj` as ONE projection of [h | x2] (FeedForward.net[2] + x2, then
+        SpatialTransformer.proj_out): (w_cat [N, in + out] fp16, bm [N] fp16), pack.pack_ff_proj_fold.  Built on first use and keyed
+        on all four parameters: an in-place edit of either layer rebuilds it."""
+        def build():
+            n = proj.out_channels
+            w_cat, bm = pack.pack_ff_proj_fold(_h(self.weight), _h(self.bias), _h(proj.weight).reshape(n, -1), _h(proj.bias))
+            return w_cat, bm.to(torch.float16).contiguous()
+        return self._packed("proj_fold", (self.weight, self.bias, proj.weight, proj.bias), build)
+
+    def _w_proj_fold_stream(self, proj):
+        """w_cat of _w_proj_fold in MFMA-fragment order for vd_gemm_wstream_cat_f16."""
+        return self._packed("proj_fold_stream", (self.weight, self.bias, proj.weight, proj.bias),
+                            lambda: pack.pack_linear_weight_stream(self._w_proj_fold(proj)[0]))
+
+    def proj_fold_ok(self, proj):
+        """Whether `proj` (a Conv2d behind this layer's output + residual) can be folded into this layer (FF_PROJ_FOLD)."""
+        c = self.out_features
+        return bool(FF_PROJ_FOLD and isinstance(proj, nn.Conv2d) and proj.kernel_size == (1, 1) and proj.stride == (1, 1)
+                    and proj.padding == (0, 0) and proj.groups == 1 and self.bias is not None and proj.bias is not None
+                    and proj.in_channels == c and proj.out_channels == c and c % 64 == 0 and self.in_features % 64 == 0)
 
     def forward(self, x, **epi):
         w, b = self._w()

@@ -178,7 +178,7 @@ def repeat_batch(t, repeat):
 def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, out=None, M=None, N=None, K=None,
          conv=None, act=ACT_NONE, alpha=1.0, out_f32=False, bias_along_m=False, batch=1, strides=(0, 0, 0, 0),
          lda0=0, lda1=0, ldw=0, ldc=0, ldr=0, c0=0, c1=0, split_k=0, out_shape=None, colsum=None, ln_eps=0.0, fixup=None,
-         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None, w_phase=None):
+         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None, w_phase=None, w_stream_cat=None):
     """out = epilogue(A @ W^T); see VdGemmDesc in include/vd_hip.h.
 
     conv = dict(Hin, Win, Hout, Wout, ksize, stride, pad, ups) selects the implicit-GEMM gather.
@@ -199,6 +199,8 @@ def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, 
     the LayerNorm folded into the NEXT projection; comes back as `out._vd_rowsums` when the planned launch can accumulate them
     (vd_gemm_row_sums_ok), else the attribute is absent and the consumer runs vd_row_stats_f16.
     ln_sums: with colsum, such a buffer describing the rows of a0 (VD_EPI_LN_SUMS) instead of the row_stats launch.
+    w_stream_cat: w ([N, c0 + c1], the weights of cat(a0, a1)) in fragment order (pack.pack_linear_weight_stream): a plain GEMM
+    whose shape fits runs on vd_gemm_wstream_cat_f16 (both sources, up to 34 chunks of K per block, statistics from the reduce).
     """
     _req(a0, "a0"); _req(a1, "a1"); _req(w, "w"); _req(bias, "bias"); _req(rowvec, "rowvec"); _req(res, "res")
     _req(colsum, "colsum", torch.float32); _req(row_sums, "row_sums", torch.int64); _req(ln_sums, "ln_sums", torch.int64)
@@ -315,6 +317,32 @@ def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, 
             nm += " M=%d N=%d K=%d" % (M, N, K)
         with _Timed(nm, 2.0 * M * N * K, 2.0 * (float(M) * (d.c0 + d.c1) + float(N) * K + float(M) * n_out + extra)):
             _check(lib().vd_conv3x3_wstream_f16(ctypes.byref(d), _ptr(w_stream), _stream()))
+        if stats is not None:
+            out._vd_stats = stats
+        return out
+    if (w_stream_cat is not None and GEMM_WSTREAM and conv is None and colsum is None and rowvec is None and skip is None
+            and row_sums is None and max(batch, 1) == 1 and lib().vd_gemm_wstream_cat_supported(ctypes.byref(d))):
+        # [a0 | a1] against one weight stream over c0 + c1 (FeedForward.net[2] with proj_out folded in at the 16x16 / 8x8 levels)
+        _req(w_stream_cat, "w_stream_cat")
+        if w_stream_cat.numel() != int(N) * int(K):
+            raise VdHipError("gemm: w_stream_cat does not match N=%d K=%d" % (int(N), int(K)))
+        d.split_k = int(split_k)
+        pns = ctypes.c_int(0)
+        _check(lib().vd_gemm_wstream_cat_plan(ctypes.byref(d), ctypes.byref(pns)))
+        d.split_k = max(pns.value, 1)
+        d.ws = workspace(lib().vd_gemm_workspace_bytes(ctypes.byref(d)), a0.device, "gemm").data_ptr()
+        stats = None
+        hw = int(stat_img_rows) if stat_img_rows else int(M)
+        if want_stats and hw % 64 == 0:   # the reduce emits partials of 64 rows
+            sbuf = torch.empty((int(M) // 64, n_out, 2), dtype=torch.float32, device=a0.device)
+            d.out_stats = sbuf.data_ptr()
+            stats = ChanStats(sbuf, hw // 64, n_out, hw)
+        nm = "gemm_wstream_cat_kernel + reduce"
+        if PROFILE_SHAPES:
+            nm += " M=%d N=%d K=%d split=%d" % (M, N, K, d.split_k)
+        extra = float(M) * n_out if res is not None else 0.0
+        with _Timed(nm, 2.0 * M * N * K, 2.0 * (float(M) * K + float(N) * K + float(M) * n_out + extra)):
+            _check(lib().vd_gemm_wstream_cat_f16(ctypes.byref(d), _ptr(w_stream_cat), _stream()))
         if stats is not None:
             out._vd_stats = stats
         return out

@@ -52,6 +52,21 @@ def pack_linear_weight_stream(w):
     return v.permute(0, 2, 3, 4, 1, 5).reshape(co // 32, ci // 64, 4, 64, 8).contiguous()
 
 
+def pack_ff_proj_fold(w2, b2, wp, bp):
+    """FeedForward.net[2] (w2 [C, 4C], b2 [C]) followed by SpatialTransformer.proj_out (wp [N, C], bp [N]) as ONE projection of
+    [h | x2]:  (x2 + h w2^T + b2) wp^T + bp == [h | x2] [wm | wp]^T + bm  with  wm = wp w2 [N, 4C],  bm = wp b2 + bp.
+    The product is formed in float64 from the given weights and rounded to their dtype ONCE (one added weight rounding; the fp16
+    rounding of the intermediate y disappears), bm in float32 arithmetic or better.  Returns (w_cat [N, 4C + C] in the dtype of
+    w2, bm float32 [N]); float64 inputs come back unrounded (the tests of the algebra)."""
+    n, c = wp.shape
+    assert w2.shape[0] == c and b2.shape == (c,) and bp.shape == (n,)
+    wp64, w264 = wp.double(), w2.double()
+    wm = wp64 @ w264
+    bm = wp64 @ b2.double() + bp.double()
+    w_cat = torch.cat([wm.to(w2.dtype), wp.to(w2.dtype)], dim=1).contiguous()
+    return w_cat, (bm if w2.dtype == torch.float64 else bm.float()).contiguous()
+
+
 def pack_conv_weight_small(w, kpad=None):
     """Same ordering, zero padded along K to a multiple of 64 (matches vd_im2col_small_f16)."""
     p = pack_conv_weight(w)
