@@ -219,6 +219,20 @@ int vd_gemm_wstream_plan(const VdGemmDesc* desc, int* nsplit);
 int vd_gemm_wstream_cat_supported(const VdGemmDesc* desc);
 int vd_gemm_wstream_cat_plan(const VdGemmDesc* desc, int* nsplit);
 int vd_gemm_wstream_cat_f16(const VdGemmDesc* desc, const void* w_stream, hipStream_t stream);
+/* vd_gemm_wstream_epi_f16: the same weight-streaming main loop over the WHOLE K in one block (K / 64 <= 32 chunks, no split: no
+ * workspace, no reduce launch) with the fused epilogue of vd_gemm_f16 in the kernel -- the LayerNorm-folded projections of a
+ * transformer block at widths 640 / 1280, norm1 -> q | k | v and norm3 -> GEGLU (lib/model_zoo/attention.py:37-45,170-176,214-218).
+ * `desc` as for vd_gemm_f16 (its `w` is not read); w_stream: the same [N][K] weights -- GEGLU-packed per 64 rows as [32 value |
+ * 32 gate] where act = VD_ACT_GEGLU -- in fragment order (pack_linear_weight_stream; for GEGLU pack_linear_weight_stream(pack_geglu(w))):
+ * value and gate of an output then sit in the same lane and register of a wave's two MFMA tiles.  Epilogue: VD_EPI_BIAS,
+ * VD_EPI_LNFOLD with either form of ln_stats ((mean, rstd) table or VD_EPI_LN_SUMS), alpha, act none or GEGLU, fp16 output in
+ * 16-byte row segments; the float sequence is gemm_f16_kernel's, so results agree with vd_gemm_f16 on the same operands bit for bit
+ * wherever the fp32 sums over K agree (both add 16-deep products in ascending K).  Two blocks share a CU (238 VGPRs, no scratch).
+ * vd_gemm_wstream_epi_supported: 1 for a plain single-source matrix (Hout = Wout = 0, ksize <= 1), batch 1, M % 128 == 0,
+ * N % 64 == 0 (GEGLU: N % 128 == 0; a block covers 256 columns, the waves past N idle), K % 64 == 0, K <= 2048, split_k <= 1,
+ * no residual / rowvec / fp32 output / in-loop statistics / out_stats / row_sums / stat_sums / skip convolution / sync. */
+int vd_gemm_wstream_epi_supported(const VdGemmDesc* desc);
+int vd_gemm_wstream_epi_f16(const VdGemmDesc* desc, const void* w_stream, hipStream_t stream);
 /* Development hook: kernel instance (0 = default) and the grid size the split over chunks aims for (256). Process-global. */
 int vd_conv3x3_wstream_set_variant(int variant, int target_blocks);
 /* The 3x3 / stride 1 / pad 1 convolution behind a nearest-2x upsample (VdGemmDesc.ups = 1: Upsample.conv of the UNet and of the

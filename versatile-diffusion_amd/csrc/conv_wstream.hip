@@ -360,3 +360,64 @@ extern "C" int vd_gemm_wstream_cat_f16(const VdGemmDesc* dp, const void* w_strea
     if (lrc != VD_OK) return lrc;
     return vd_gemm_launch_reduce(&a, nsplit, stream);
 }
+
+
+// ---- the same main loop over the WHOLE K of a block with the fused epilogue in the kernel: no slabs, no reduce launch -------
+// (the LayerNorm-folded q | k | v and GEGLU projections of a transformer block at widths 640 / 1280: K = C <= 20 chunks.)
+// Entries of their own: what the entries above answer and launch stays as it is.
+namespace {
+const char* gwe_reject(const VdGemmDesc& d) {
+    if (d.ksize > 1 || d.stride > 1 || d.pad != 0 || d.ups != 0 || d.Hout > 0 || d.Wout > 0 || d.batch != 1 || d.a1 != nullptr) return "a plain single-source, unbatched GEMM (Hout = Wout = 0)";
+    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.M % 128 != 0 || d.N % 64 != 0 || d.K % 64 != 0) return "M % 128 == 0, N % 64 == 0, K % 64 == 0";
+    if (d.K / 64 > GW_MAXC) return "K <= 2048 (the unrolled chunk sequence; this entry does not split K)";
+    if (d.split_k > 1) return "no split over K";
+    if (d.flags & ~(VD_EPI_BIAS | VD_EPI_LNFOLD | VD_EPI_LN_SUMS)) return "an fp16 epilogue of bias and LayerNorm fold (no residual, rowvec, fp32 output, in-loop statistics)";
+    if ((d.flags & VD_EPI_LN_SUMS) && !(d.flags & VD_EPI_LNFOLD)) return "VD_EPI_LN_SUMS only with VD_EPI_LNFOLD";
+    if (d.act != VD_ACT_NONE && d.act != VD_ACT_GEGLU) return "act none or GEGLU";
+    if (d.act == VD_ACT_GEGLU && d.N % 128 != 0) return "GEGLU with N % 128 == 0";
+    if (d.out_stats != nullptr || d.row_sums != nullptr || d.stat_sums != nullptr || d.skip_a0 != nullptr || d.skip_w != nullptr || d.sync != nullptr)
+        return "no out_stats, row_sums, stat_sums, folded skip convolution or arrival counters";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int vd_gemm_wstream_epi_supported(const VdGemmDesc* dp) {
+    if (dp == nullptr) return 0;
+    VdGemmDesc d = *dp;
+    if (d.batch <= 0) d.batch = 1;
+    return gwe_reject(d) == nullptr ? 1 : 0;
+}
+
+extern "C" int vd_gemm_wstream_epi_f16(const VdGemmDesc* dp, const void* w_stream, hipStream_t stream) {
+    VD_REQUIRE(dp != nullptr && w_stream != nullptr, "vd_gemm_wstream_epi_f16: null argument");
+    {
+        VdGemmDesc chk = *dp;
+        if (chk.batch <= 0) chk.batch = 1;
+        const char* why = gwe_reject(chk);
+        VD_REQUIRE(why == nullptr, "vd_gemm_wstream_epi_f16 takes %s", why ? why : "");
+    }
+    VdGemmDesc tmp = *dp;
+    tmp.w = w_stream;   // the K-contiguous weights are not read on this path
+    GemmArgs a;
+    const int rc = vd_gemm_normalise(&tmp, &a);   // pointers, flags and defaults as vd_gemm_f16 validates them
+    if (rc != VD_OK) return rc;
+    const VdGemmDesc& d = a.d;
+    const int n_out = d.act == VD_ACT_GEGLU ? d.N / 2 : d.N;
+    VD_REQUIRE(((size_t)w_stream & 15) == 0 && d.lda0 % 8 == 0 && d.lda0 >= d.K, "vd_gemm_wstream_epi_f16: w_stream must be 16-byte aligned, lda a multiple of 8 that covers K");
+    VD_REQUIRE(((size_t)d.out & 15) == 0 && d.ldc % 8 == 0 && d.ldc >= n_out, "vd_gemm_wstream_epi_f16: out must be 16-byte aligned, ldc a multiple of 8 that covers the output row");
+    VD_REQUIRE(!(d.flags & VD_EPI_BIAS) || ((size_t)d.bias & 7) == 0, "vd_gemm_wstream_epi_f16: bias must be 8-byte aligned");
+    if (d.flags & VD_EPI_LNFOLD)
+        VD_REQUIRE(d.ln_stats != nullptr, "vd_gemm_wstream_epi_f16: the LayerNorm fold needs ln_stats");
+    GwEpiArgs w;
+    w.a = reinterpret_cast<const f16*>(d.a0); w.wp = reinterpret_cast<const uint4*>(w_stream); w.ws = nullptr;
+    w.lda = d.lda0; w.M = d.M; w.N = d.N;
+    w.nchunks = d.K / 64; w.cps = w.nchunks; w.nsplit = 1;
+    w.tiles_m = d.M / 128; w.tiles_n = (d.N + 255) / 256;
+    w.a_bytes = a.a0_bytes;
+    w.out = reinterpret_cast<f16*>(d.out); w.bias = reinterpret_cast<const f16*>(d.bias);
+    w.colsum = d.colsum; w.ln_stats = d.ln_stats;
+    w.ldc = d.ldc; w.flags = d.flags; w.act = d.act; w.K = d.K;
+    w.alpha = d.alpha; w.ln_eps = d.ln_eps;
+    hipLaunchKernelGGL((gemm_wstream_kernel<GW_MAXC, GwEpiArgs>), dim3(w.tiles_m * w.tiles_n), dim3(256), 2 * GW_TILE, stream, w);
+    return vd_check_launch("vd_gemm_wstream_epi_f16");
+}

@@ -30,6 +30,19 @@ struct GwCatArgs : GwArgs {
     unsigned a1_bytes;
 };
 
+// ... of the whole-K entry with the fused epilogue (vd_gemm_wstream_epi_f16): nsplit == 1, no slabs (ws unused); the epilogue of
+// gemm_f16_kernel (LayerNorm fold, bias, GEGLU, alpha) runs on the accumulators where they sit.  N may end inside a block's 256
+// columns (N % 64 == 0): a wave whose 64 columns lie past N streams the last valid panel instead -- every wave issues the same
+// requests, the hand-counted waits of the chunk sequence hold in all of them -- and skips MFMAs and epilogue.
+struct GwEpiArgs : GwArgs {
+    f16* out;
+    const f16* bias;         // [N] (packed order with GEGLU), read when flags has VD_EPI_BIAS
+    const float* colsum;     // VD_EPI_LNFOLD: [N]
+    const float* ln_stats;   // VD_EPI_LNFOLD: (mean, rstd) per row, or the int64 row sums with VD_EPI_LN_SUMS
+    int ldc, flags, act, K;
+    float alpha, ln_eps;
+};
+
 constexpr int GW_TILE = 128 * 128;   // bytes of one activation tile [128 rows][64 halfs]
 constexpr int GW_MAXC = 32;          // chunks per block (the chunk sequence is unrolled)
 constexpr int GW_MAXC_LONG = 34;     // ... of the long instance: K = 6400 (A = [h | x2], 5 x 1280) as 3 splits -- 240 blocks, one round
@@ -44,9 +57,143 @@ __device__ __forceinline__ void gw_static_for(F&& f) {
 
 // MAXC: length of the unrolled chunk sequence.  P = GwCatArgs: the K axis is the concatenation of two activation matrices; the
 // weights stay ONE fragment-order stream over the concatenated K.
+// ---- fused epilogue of the whole-K instance (P = GwEpiArgs).  A lane owns row i * 32 + l31 and the columns j * 32 + 8 g + 4 hi ..
+// + 3 of its wave's 64 -- the ownership of gemm_f16_kernel's accumulators -- and the float sequence is that kernel's (part 1 of its
+// epilogue in gemm_kernel.h), operation for operation: fold  fmaf(rstd, acc, nmr * colsum[n]) + bias'[n]  for GEGLU,
+// fmaf(rstd, acc, fmaf(nmr, colsum[n], bias'[n])) * alpha  plain, with rstd = 1 and no colsum term without the fold.  With the
+// GEGLU packing ([32 value | 32 gate] per 64 weight rows) a wave's j = 0 tile holds the values and j = 1 the gates of its 32 outputs.
+// Wait counts: the operands (row statistics, colsum, bias) are requested BEHIND the last chunk, as compiler-tracked loads -- they
+// enter no hand-counted wait of the chunk sequence; the clamped weight re-reads still in flight are older and retire first.
+// The fp16 tile leaves through the two activation buffers, free after the last chunk once every wave has passed the barrier in
+// front (another wave may still read the last tile): a wave owns 8 KiB -- [128 rows][32 outputs] with GEGLU, else [64 rows][64
+// columns] in two passes -- swizzled as the operand tiles are, and stores it as 16-byte segments of 64- / 128-byte row runs.
+__device__ __forceinline__ void gw_epilogue(const GwEpiArgs& p, const f32x16 (&acc)[4][2], char* smem, int m0, int n0, bool active,
+                                            int wave_s, int lane) {
+    const int hi = lane >> 5, l31 = lane & 31;
+    const bool lnf = (p.flags & VD_EPI_LNFOLD) != 0, ln_sums = (p.flags & VD_EPI_LN_SUMS) != 0;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    uint4 lnst_r[4];
+    U2H4 bias_r[8];
+    float4 cs_r[8];
+    {
+        EpiCtx e = {};
+        e.bias = p.bias;
+        e.flags = p.flags;
+        epi_load_bias<2>(e, p.N, n0 + 4 * hi, bias_r, true);   // columns past N (a wave that is not active) read zeros
+        epi_load_lnstats<4>(p.ln_stats, p.M, 0, m0 + l31, lnst_r, lnf, ln_sums, p.M);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.colsum), 0, lnf ? p.N * 4 : 0, 0x00020000);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const vd_u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (n0 + j * 32 + 8 * g + 4 * hi) * 4, 0, 0);
+                cs_r[j * 4 + g] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+            }
+    }
+    __syncthreads();   // every wave has left the last activation tile
+    char* cs = smem + wave_s * 8192;
+    auto row_stats = [&](int i, float& ln_rstd, float& ln_nmr) {   // y = rstd * acc - (mean * rstd) * colsum[n] + bias'[n]
+        ln_rstd = 1.f;
+        ln_nmr = 0.f;
+        if (lnf) {
+            const uint4 st = lnst_r[i];
+            if (ln_sums) {   // (sum, sum of squares) from the producer's row_sums
+                ln_sums_decode(st, p.K, p.ln_eps, ln_rstd, ln_nmr);
+            } else {
+                ln_rstd = __uint_as_float(st.y);
+                ln_nmr = -__uint_as_float(st.x) * ln_rstd;
+            }
+        }
+    };
+    if (p.act == VD_ACT_GEGLU) {
+        if (active) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float ln_rstd, ln_nmr;
+                row_stats(i, ln_rstd, ln_nmr);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const U2H4 bv = bias_r[g], bg = bias_r[4 + g];
+                    float4 cv = make_float4(0.f, 0.f, 0.f, 0.f), cg = cv;
+                    if (lnf) {
+                        cv = cs_r[g];
+                        cg = cs_r[4 + g];
+                    }
+                    const float cva[4] = {cv.x, cv.y, cv.z, cv.w}, cga[4] = {cg.x, cg.y, cg.z, cg.w};
+                    U2H4 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float v = fmaf(ln_rstd, acc[i][0][g * 4 + q], ln_nmr * cva[q]) + (float)bv.e[q];
+                        const float gt = fmaf(ln_rstd, acc[i][1][g * 4 + q], ln_nmr * cga[q]) + (float)bg.e[q];
+                        o.e[q] = (f16)(v * vd_gelu_erf(gt) * p.alpha);
+                    }
+                    *reinterpret_cast<uint2*>(cs + lds_off_kb<32>(i * 32 + l31, g) + hi * 8) = o.u;
+                }
+            }
+        }
+        __syncthreads();
+        if (active) {
+            f16* dst = p.out + (size_t)m0 * p.ldc + (n0 >> 1);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int s = k * 64 + lane, row = s >> 2, slot = s & 3;
+                *reinterpret_cast<uint4*>(dst + (size_t)row * p.ldc + slot * 8) = *reinterpret_cast<const uint4*>(cs + lds_off_kb<32>(row, slot));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            if (pass > 0) __syncthreads();   // the stores of the previous pass have read the tile
+            if (active) {
+#pragma unroll
+                for (int ii = 0; ii < 2; ++ii) {
+                    const int i = pass * 2 + ii;
+                    float ln_rstd, ln_nmr;
+                    row_stats(i, ln_rstd, ln_nmr);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            float bq[4] = {0.f, 0.f, 0.f, 0.f};
+                            if (p.flags & VD_EPI_BIAS) {
+                                const U2H4 t = bias_r[j * 4 + g];
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) bq[q] = (float)t.e[q];
+                            }
+                            if (lnf) {
+                                const float4 c4 = cs_r[j * 4 + g];
+                                bq[0] = fmaf(ln_nmr, c4.x, bq[0]);
+                                bq[1] = fmaf(ln_nmr, c4.y, bq[1]);
+                                bq[2] = fmaf(ln_nmr, c4.z, bq[2]);
+                                bq[3] = fmaf(ln_nmr, c4.w, bq[3]);
+                            }
+                            U2H4 o;
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) o.e[q] = (f16)(fmaf(ln_rstd, acc[i][j][g * 4 + q], bq[q]) * p.alpha);
+                            *reinterpret_cast<uint2*>(cs + lds_off_kb<64>(ii * 32 + l31, j * 4 + g) + hi * 8) = o.u;
+                        }
+                }
+            }
+            __syncthreads();
+            if (active) {
+                f16* dst = p.out + (size_t)(m0 + pass * 64) * p.ldc + n0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int s = k * 64 + lane, row = s >> 3, slot = s & 7;
+                    *reinterpret_cast<uint4*>(dst + (size_t)row * p.ldc + slot * 8) = *reinterpret_cast<const uint4*>(cs + lds_off_kb<64>(row, slot));
+                }
+            }
+        }
+    }
+}
+
+// P = GwEpiArgs: the whole K in one block, the fused epilogue in place of the slab store, two blocks per CU (one wave of each per
+// SIMD: a block keeps the matrix pipe about 40 % busy).
 template <int MAXC, class P>
-__global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const P p) {
+__global__ __launch_bounds__(256, (std::is_same<P, GwEpiArgs>::value ? 2 : 1)) void gemm_wstream_kernel(const P p) {
     constexpr bool CAT = std::is_same<P, GwCatArgs>::value;
+    constexpr bool EPI = std::is_same<P, GwEpiArgs>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -113,7 +260,12 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const P p) {
     };
 
     // ---- weight stream of this wave: two n tiles, 4 fragments (1 KiB each) per chunk and tile, chunks contiguous
-    const int nt0 = n0 >> 5;
+    bool active = true;   // EPI: false in a wave whose columns lie past N (wave-uniform)
+    int nt0 = n0 >> 5;
+    if constexpr (EPI) {
+        active = n0 < p.N;
+        if (!active) nt0 = (p.N >> 5) - 2;
+    }
     const uint4* wq0 = p.wp + (size_t)nt0 * p.nchunks * 256 + lane;
     const uint4* wq1 = p.wp + (size_t)(nt0 + 1) * p.nchunks * 256 + lane;
     const int c_last = c_end - 1;
@@ -161,18 +313,20 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const P p) {
         const char* st = smem + par * GW_TILE;
         gw_static_for<0, 4>([&](auto kt) {
             constexpr int ks = decltype(kt)::value;
-            f16x8 bf[4];
+            if (!EPI || active) {
+                f16x8 bf[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                U4H8 v;
-                v.u = *reinterpret_cast<const uint4*>(st + rd[ks] + i * 32 * 128);
-                bf[i] = v.h;
+                for (int i = 0; i < 4; ++i) {
+                    U4H8 v;
+                    v.u = *reinterpret_cast<const uint4*>(st + rd[ks] + i * 32 * 128);
+                    bf[i] = v.h;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[par][ks][j].h, bf[i], acc[i][j], 0, 0, 0);
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[par][ks][j].h, bf[i], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             // issued whether or not chunk c + 2 is this block's (clamped): every chunk adds exactly 8 weight loads behind its
             // DMA pieces -- except where no block has a chunk lc + 2, which the wait of chunk lc + 1 above accounts for
@@ -189,20 +343,24 @@ __global__ __launch_bounds__(256, 1) void gemm_wstream_kernel(const P p) {
         if (lc < ncl) chunk(lt);
     });
 
-    // ---- fp32 slab of this split for the reduce kernel, straight from registers (4 consecutive floats per lane and group)
-    float* base = p.ws + (size_t)split * (size_t)p.M * p.N;
+    if constexpr (EPI) {
+        gw_epilogue(p, acc, smem, m0, n0, active, wave_s, lane);
+    } else {
+        // ---- fp32 slab of this split for the reduce kernel, straight from registers (4 consecutive floats per lane and group)
+        float* base = p.ws + (size_t)split * (size_t)p.M * p.N;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = m0 + i * 32 + l31;
+        for (int i = 0; i < 4; ++i) {
+            const int row = m0 + i * 32 + l31;
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int col = n0 + j * 32 + 8 * g + 4 * hi;
-                if (row < p.M)
-                    *reinterpret_cast<float4*>(base + (size_t)row * p.N + col) =
-                        make_float4(acc[i][j][g * 4], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
-            }
+                for (int g = 0; g < 4; ++g) {
+                    const int col = n0 + j * 32 + 8 * g + 4 * hi;
+                    if (row < p.M)
+                        *reinterpret_cast<float4*>(base + (size_t)row * p.N + col) =
+                            make_float4(acc[i][j][g * 4], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+                }
+        }
     }
 }
 

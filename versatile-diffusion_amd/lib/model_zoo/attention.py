@@ -31,7 +31,16 @@ class GEGLU(nn.Module, PackCache):
             return ops.linear(x, wp, bp, act=ops.ACT_GEGLU)
 
         wp, bp, cs = self.folded(ln)
-        return ops.linear(x, wp, bp, act=ops.ACT_GEGLU, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums)
+        kw = {}
+        if hip_layers.wstream_epi_level("geglu", x.numel() // x.shape[-1], x.shape[-1]):
+            kw["w_stream_epi"] = self.folded_stream(ln)
+        return ops.linear(x, wp, bp, act=ops.ACT_GEGLU, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums, **kw)
+
+    def folded_stream(self, ln):
+        """The packed weight of folded() in MFMA-fragment order for vd_gemm_wstream_epi_f16 (a wave's two 32-row tiles are the value
+        and the gate rows of its 32 outputs); keyed on the same parameters."""
+        return self._packed("geglu_ln_stream", (self.proj.weight, self.proj.bias, ln.weight, ln.bias),
+                            lambda: pack.pack_linear_weight_stream(self.folded(ln)[0]))
 
     def folded(self, ln):
         """(gamma-folded GEGLU-packed weight, beta-folded packed bias, fp32 row sums of the packed weight), cached."""
@@ -125,6 +134,11 @@ class CrossAttention(nn.Module, PackCache):
         return self._packed("qkv_ln", (self.to_q.weight, self.to_k.weight, self.to_v.weight, ln.weight, ln.bias),
                             lambda: fold_layernorm(self._w_qkv(), None, ln))
 
+    def _w_qkv_ln_stream(self, ln):
+        """The weight of _w_qkv_ln in MFMA-fragment order for vd_gemm_wstream_epi_f16; keyed on the same parameters."""
+        return self._packed("qkv_ln_stream", (self.to_q.weight, self.to_k.weight, self.to_v.weight, ln.weight, ln.bias),
+                            lambda: pack.pack_linear_weight_stream(self._w_qkv_ln(ln)[0]))
+
     def _w_q_ln(self, ln):
         return self._packed("q_ln", (self.to_q.weight, ln.weight, ln.bias),
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
@@ -151,7 +165,10 @@ class CrossAttention(nn.Module, PackCache):
                 qkv = ops.linear(x, self._w_qkv())
             else:
                 w, b, cs = self._w_qkv_ln(ln)
-                qkv = ops.linear(x, w, b, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums)
+                kw = {}
+                if hip_layers.wstream_epi_level("qkv", x.numel() // x.shape[-1], x.shape[-1]):
+                    kw["w_stream_epi"] = self._w_qkv_ln_stream(ln)
+                qkv = ops.linear(x, w, b, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums, **kw)
             a = ops.attention(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, scale=self.scale)
         else:
             if kv is None:

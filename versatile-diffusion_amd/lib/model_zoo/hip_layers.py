@@ -21,6 +21,23 @@ LN_FOLD = os.environ.get("VD_LN_FOLD", "1") != "0"
 # two launches.  VD_FF_PROJ_FOLD=0: the two launches everywhere
 FF_PROJ_FOLD = os.environ.get("VD_FF_PROJ_FOLD", "1") != "0"
 
+# The LayerNorm-folded projections of a transformer block on vd_gemm_wstream_epi_f16 (ops.GEMM_WSTREAM_EPI): the fragment-order
+# pack is handed over where the launch measured faster than gemm_f16_kernel's inside a UNet forward (profiles/HISTORY.md R8):
+# (lowest, highest) row count (tokens x batch) per (projection, inner width); other widths stay on gemm_f16_kernel (320 has its
+# own kernels).  Measured: 8192 rows at width 640, 512 and 2048 rows at width 1280 -- all six launches faster; the bound at width 1280 is twice the
+# largest measured row count.  Development switch for A/B runs: VD_WSTREAM_EPI_ROWS="qkv640=128:8192,geglu1280=0:0,..." replaces entries.
+WSTREAM_EPI_ROWS = {("qkv", 640): (128, 8192), ("qkv", 1280): (128, 4096), ("geglu", 640): (128, 8192), ("geglu", 1280): (128, 4096)}
+for _item in filter(None, os.environ.get("VD_WSTREAM_EPI_ROWS", "").split(",")):
+    _k, _v = _item.split("=")
+    _kind = "qkv" if _k.startswith("qkv") else "geglu"
+    WSTREAM_EPI_ROWS[(_kind, int(_k[len(_kind):]))] = tuple(int(v) for v in _v.split(":"))
+
+
+def wstream_epi_level(kind, rows, width):
+    """Whether the `kind` ("qkv" / "geglu") projection of `rows` rows at inner width `width` takes the weight-streaming entry."""
+    lo, hi = WSTREAM_EPI_ROWS.get((kind, int(width)), (0, 0))
+    return bool(rows % 128 == 0 and lo <= rows <= hi and LN_FOLD and ops.GEMM_WSTREAM_EPI)
+
 
 def _ver(t):
     return None if t is None else (t.data_ptr(), t._version, t.dtype, str(t.device), tuple(t.shape))

@@ -65,6 +65,8 @@ PROTOTYPES = {
     "vd_gemm_wstream_cat_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),
     "vd_gemm_wstream_cat_plan": (_I, [ctypes.POINTER(VdGemmDesc), ctypes.POINTER(ctypes.c_int)]),
     "vd_gemm_wstream_cat_f16": (_I, [ctypes.POINTER(VdGemmDesc), _P, _P]),
+    "vd_gemm_wstream_epi_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),
+    "vd_gemm_wstream_epi_f16": (_I, [ctypes.POINTER(VdGemmDesc), _P, _P]),
     "vd_conv3x3_wstream_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),
     "vd_conv3x3_wstream_set_variant": (_I, [_I, _I]),
     "vd_conv3x3_ups_phase_supported": (_I, [ctypes.POINTER(VdGemmDesc)]),

@@ -178,7 +178,7 @@ def repeat_batch(t, repeat):
 def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, out=None, M=None, N=None, K=None,
          conv=None, act=ACT_NONE, alpha=1.0, out_f32=False, bias_along_m=False, batch=1, strides=(0, 0, 0, 0),
          lda0=0, lda1=0, ldw=0, ldc=0, ldr=0, c0=0, c1=0, split_k=0, out_shape=None, colsum=None, ln_eps=0.0, fixup=None,
-         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None, w_phase=None, w_stream_cat=None):
+         want_stats=False, stat_img_rows=0, w_stream=None, skip=None, row_sums=None, ln_sums=None, w_phase=None, w_stream_cat=None, w_stream_epi=None):
     """out = epilogue(A @ W^T); see VdGemmDesc in include/vd_hip.h.
 
     conv = dict(Hin, Win, Hout, Wout, ksize, stride, pad, ups) selects the implicit-GEMM gather.
@@ -201,6 +201,10 @@ def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, 
     ln_sums: with colsum, such a buffer describing the rows of a0 (VD_EPI_LN_SUMS) instead of the row_stats launch.
     w_stream_cat: w ([N, c0 + c1], the weights of cat(a0, a1)) in fragment order (pack.pack_linear_weight_stream): a plain GEMM
     whose shape fits runs on vd_gemm_wstream_cat_f16 (both sources, up to 34 chunks of K per block, statistics from the reduce).
+    w_stream_epi: w (GEGLU-packed where act is ACT_GEGLU) in fragment order (pack.pack_linear_weight_stream): a plain GEMM with
+    K <= 2048 whose epilogue is bias / LayerNorm fold / GEGLU / alpha runs on vd_gemm_wstream_epi_f16 (whole K per block, the
+    epilogue in the kernel) where vd_gemm_wstream_epi_supported says so; GEMM_WSTREAM_EPI off, or a call it refuses (a residual,
+    row_sums, statistics, ...), stays on the launches below.
     """
     _req(a0, "a0"); _req(a1, "a1"); _req(w, "w"); _req(bias, "bias"); _req(rowvec, "rowvec"); _req(res, "res")
     _req(colsum, "colsum", torch.float32); _req(row_sums, "row_sums", torch.int64); _req(ln_sums, "ln_sums", torch.int64)
@@ -319,6 +323,19 @@ def gemm(a0, w, *, a1=None, bias=None, rowvec=None, rows_per_batch=0, res=None, 
             _check(lib().vd_conv3x3_wstream_f16(ctypes.byref(d), _ptr(w_stream), _stream()))
         if stats is not None:
             out._vd_stats = stats
+        return out
+    if (w_stream_epi is not None and GEMM_WSTREAM_EPI and conv is None and a1 is None and rowvec is None and res is None and skip is None
+            and row_sums is None and not want_stats and not out_f32 and not bias_along_m and max(batch, 1) == 1
+            and lib().vd_gemm_wstream_epi_supported(ctypes.byref(d))):
+        # whole K per block, epilogue on the accumulators (norm1 -> q | k | v and norm3 -> GEGLU at widths 640 / 1280)
+        _req(w_stream_epi, "w_stream_epi")
+        if w_stream_epi.numel() != int(N) * int(K):
+            raise VdHipError("gemm: w_stream_epi does not match N=%d K=%d" % (int(N), int(K)))
+        nm = "gemm_wstream_epi_kernel" + (" geglu" if act == ACT_GEGLU else "")
+        if PROFILE_SHAPES:
+            nm += " M=%d N=%d K=%d cls=%d" % (M, N, K, (1 if act == ACT_GEGLU else 0) | (2 if colsum is not None else 0))
+        with _Timed(nm, 2.0 * M * N * K, 2.0 * (float(M) * K + float(N) * K + float(M) * n_out)):
+            _check(lib().vd_gemm_wstream_epi_f16(ctypes.byref(d), _ptr(w_stream_epi), _stream()))
         return out
     if (w_stream_cat is not None and GEMM_WSTREAM and conv is None and colsum is None and rowvec is None and skip is None
             and row_sums is None and max(batch, 1) == 1 and lib().vd_gemm_wstream_cat_supported(ctypes.byref(d))):
@@ -521,6 +538,9 @@ GEMM_WSTREAM = os.environ.get("VD_GEMM_WSTREAM", "1") != "0"   # long-K small-M 
 # the 3x3 convolution behind a nearest-2x upsample as four 2x2 phase convolutions with pre-summed weights (vd_conv3x3_ups_phase_f16:
 # 4 / 9 of the multiplies; exact algebra with one added weight rounding, so not bit-identical to the upsampled form).  0 = the
 # upsampled 3x3 form on vd_gemm_f16
+# the LayerNorm-folded q | k | v and GEGLU projections on the weight-streaming kernel with its own epilogue (vd_gemm_wstream_epi_f16);
+# 0 = today's gemm_f16_kernel launches.  Which levels hand the fragment-order pack over: lib/model_zoo/attention.py (wstream_epi_level)
+GEMM_WSTREAM_EPI = os.environ.get("VD_GEMM_WSTREAM_EPI", "1") != "0"
 UPS_PHASE = os.environ.get("VD_UPS_PHASE", "1") != "0"
 WSTREAM = os.environ.get("VD_WSTREAM", "1") != "0"   # development switch: 0 = the 8x8-level 3x3 convolutions stay on gemm_f16_kernel
 ROW320 = os.environ.get("VD_GEMM_ROW320", "1") != "0"   # development switch: 0 = the K = 320 projections stay on gemm_f16_kernel
