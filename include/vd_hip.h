@@ -530,6 +530,39 @@ int vd_cfg_dpmpp_sde_step_dev_rs_f16(const void* x, const void* eps, float* x0_h
                                      int64_t per_sample, int guided, const float* coef, const int64_t* seeds, const int* rng,
                                      const float* kfac, hipStream_t stream);
 
+/* Classifier-free-guidance combine + UniPC corrector + predictor (Zhao et al. 2023, variant bh2, data prediction; what
+ * diffusers' UniPCMultistepScheduler(solver_type="bh2", predict_x0=True) computes) of one sampling step in one pass, step
+ * scalars in device memory: one captured HIP graph of a step serves every step.  Both updates are linear in their operands
+ * and the host collapses them (float64, unipc.unipc_coef_table) into one fp32 row
+ *   coef[16] = {guidance scale s, 1/sqrt(a_t), sqrt(1 - a_t), corrector on (0 / 1), c_x, c_1, c_2, c_3, c_t,
+ *               p_x, p_t, p_1, p_2, hist, 0, 0}
+ * hist = min(steps of this call already run, 3): how many of the data predictions m_1 (the most recent), m_2, m_3 exist.
+ *   e      = fma(s, e_c - e_u, e_u), or e_u when guided == 0          (the _rs twin: e' = kfac[i / per_sample] * e)
+ *   m_t    = fma(-sqrt(1 - a_t), e, x) * (1/sqrt(a_t))
+ *   x_c    = fma(c_x, x_last, fma(c_3, m_3, fma(c_2, m_2, fma(c_1, m_1, c_t * m_t))))   corrector on; else x_c = x (widened)
+ *   x_next = fma(p_x, x_c, fma(p_2, m_2, fma(p_1, m_1, p_t * m_t)))
+ *   then x_last = x_c, (m_1, m_2, m_3) = (m_t, m_1, m_2), pred_x0 = m_t (fp16, may be NULL)
+ * Roundings (part of the contract): every line above is fp32 and every product-sum is ONE fma, nested in the order written
+ * (innermost first); a term whose coefficient is 0 is left out of the chain, not multiplied; x_next and pred_x0 are the fp32
+ * results rounded to fp16 as a rounding of their own (never a sum rounded straight to fp16).  The 16-byte loop (every pointer
+ * 16-byte aligned; elements [0, n/8*8), 8 per lane) and the scalar loop (every other element) follow the same rule: an
+ * element has the same bits on either.
+ * What is read: x_last only with the corrector on; m_3 only when c_3 != 0; m_1 when hist >= 1 and m_2 when hist >= 2 (every
+ * non-zero coefficient implies that, and the shift of the history needs them).  A row with hist == 0 -- the first step of a
+ * call -- reads no state, so the state may be uninitialised there, and it writes m_1 = m_2 = m_3 = m_t: after any step all
+ * four state buffers hold defined values.
+ * x, x_next, pred_x0: fp16 [n]; eps: fp16 [e_uncond ; e_cond] (2n) when guided != 0, else [n]; x_last, m1, m2, m3: fp32 [n],
+ * four distinct buffers.  x_next may alias x.  Does not allocate or synchronise (capturable).  Returns < 0 (vd_last_error)
+ * for null pointers (pred_x0 may be NULL), n <= 0, or state buffers that coincide; the _rs twin also for the errors of the
+ * other _rs entry points (a null kfac, per_sample <= 0, n not a multiple of per_sample, guided == 0).  With every
+ * kfac[b] == 1.0f the twin gives the plain entry point's bits; a lane of its 16-byte loop that straddles samples looks the
+ * factor up per element. */
+int vd_cfg_unipc_step_dev_f16(const void* x, const void* eps, float* x_last, float* m1, float* m2, float* m3, void* x_next,
+                              void* pred_x0, int64_t n, int guided, const float* coef, hipStream_t stream);
+int vd_cfg_unipc_step_dev_rs_f16(const void* x, const void* eps, float* x_last, float* m1, float* m2, float* m3, void* x_next,
+                                 void* pred_x0, int64_t n, int64_t per_sample, int guided, const float* coef,
+                                 const float* kfac, hipStream_t stream);
+
 /* Masked blend of blended latent diffusion (inpainting; not in the reference), after a sampler step lands on a_prev:
  *   out = m x + (1 - m) (ca x0 + cn noise),  coef[2] = {ca, cn} = {sqrt(a_prev), sqrt(1 - a_prev)} (or {1, 0} on the
  *   last step) in device memory, fp32 math, one fp16 rounding.

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # VD_BUILD_OUT: development builds of variants (VD_EXTRA_DEFS) next to the product library, for VD_HIP_LIB A/B runs
 OUT = os.environ.get("VD_BUILD_OUT") or os.path.join(HERE, "libvd_hip.so")
-SOURCES = ["gemm.hip", "conv_halo.hip", "conv_ups_phase.hip", "conv_wstream.hip", "ff_fused.hip", "ff_chain.hip", "gemm_row320.hip", "norm.hip", "gn_fused.hip", "attention.hip", "xattn_fused.hip", "elementwise.hip", "preprocess.hip", "lowrank.hip", "noise.hip"]
+SOURCES = ["gemm.hip", "conv_halo.hip", "conv_ups_phase.hip", "conv_wstream.hip", "ff_fused.hip", "ff_chain.hip", "gemm_row320.hip", "norm.hip", "gn_fused.hip", "attention.hip", "xattn_fused.hip", "elementwise.hip", "preprocess.hip", "lowrank.hip", "noise.hip", "unipc.hip"]
 # every header under csrc/ (a kernel header that is not hashed would let a stale library pass the stamp check)
 import glob
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "vd_hip.h")]
@@ -36,7 +36,9 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # update duplicate every step scalar into a scalar register pair per use; with the inlined logf / sincospif of
                # the generator that spills 33 scalar registers.  The update's roundings are written out in the source, so
                # this flag does not decide its bits.
-               "noise.hip": ["-fno-slp-vectorize"]}
+               "noise.hip": ["-fno-slp-vectorize"],
+               # the UniPC update: the same unrolled 8-element form, the same flag; its roundings are written out too
+               "unipc.hip": ["-fno-slp-vectorize"]}
 
 
 def _digest():

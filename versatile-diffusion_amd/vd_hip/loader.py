@@ -116,6 +116,8 @@ PROTOTYPES = {
     "vd_cfg_ddim_step_dev_rs_f16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P]),
     "vd_cfg_dpmpp_step_dev_rs_f16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P]),
     "vd_cfg_dpmpp_sde_step_dev_rs_f16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _P]),
+    "vd_cfg_unipc_step_dev_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    "vd_cfg_unipc_step_dev_rs_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P]),
     "vd_masked_blend_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, _P]),
     "vd_q_sample_f16": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),
     "vd_nchw_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -1192,6 +1192,49 @@ def cfg_dpmpp_sde_step_dev_rs(x, eps, coef, x0_hist, seeds, rng, kfac, *, guided
     return x_next, pred_x0
 
 
+def _unipc_operands(x, eps, coef, state, guided, x_next, pred_x0):
+    """The operand checks of the UniPC updates; state = (x_last, m1, m2, m3), four distinct fp32 buffers.  Returns
+    n = x.numel()."""
+    _req(x, "x"); _req(eps, "eps"); _req(coef, "coef", torch.float32); _req(x_next, "x_next"); _req(pred_x0, "pred_x0")
+    if len(state) != 4:
+        raise VdHipError("state holds %d tensors, expected (x_last, m1, m2, m3)" % len(state))
+    n = _eps_count(x, eps, guided)
+    named = list(zip(state, ("x_last", "m1", "m2", "m3")))
+    for t, name in named:
+        if t is None:
+            raise VdHipError("%s is required" % name)
+        _req(t, name, torch.float32)
+    for t, name in named + [(x_next, "x_next"), (pred_x0, "pred_x0")]:
+        if t is not None and t.numel() != n:
+            raise VdHipError("%s has %d elements, expected %d" % (name, t.numel(), n))
+    if len({t.data_ptr() for t in state}) != 4:
+        raise VdHipError("x_last, m1, m2, m3 must be four distinct buffers")
+    if coef.numel() < 16:
+        raise VdHipError("coef has %d elements, expected 16" % coef.numel())
+    return n
+
+
+def cfg_unipc_step_dev(x, eps, coef, state, *, guided, x_next, pred_x0=None):
+    """CFG + UniPC corrector + predictor of one step with the step scalars in a device fp32[16] tensor (a row of
+    unipc.unipc_coef_table).  state = (x_last, m1, m2, m3): fp32 buffers of x's size, read as far as the row says and
+    rewritten (x_last = the corrected latent, m1..m3 = the shifted data predictions).  Writes into caller-owned buffers;
+    x_next may be x."""
+    n = _unipc_operands(x, eps, coef, state, guided, x_next, pred_x0)
+    _check(lib().vd_cfg_unipc_step_dev_f16(_ptr(x), _ptr(eps), *[_ptr(t) for t in state], _ptr(x_next), _ptr(pred_x0), n,
+                                           1 if guided else 0, _ptr(coef), _stream()))
+    return x_next, pred_x0
+
+
+def cfg_unipc_step_dev_rs(x, eps, coef, state, kfac, *, guided, x_next, pred_x0=None):
+    """cfg_unipc_step_dev with the guidance rescale (kfac: device fp32 [B], one factor per sample of x)."""
+    _req_guided(guided)
+    n = _unipc_operands(x, eps, coef, state, guided, x_next, pred_x0)
+    per = _per_sample(x, kfac, n)
+    _check(lib().vd_cfg_unipc_step_dev_rs_f16(_ptr(x), _ptr(eps), *[_ptr(t) for t in state], _ptr(x_next), _ptr(pred_x0), n,
+                                              per, 1, _ptr(coef), _ptr(kfac), _stream()))
+    return x_next, pred_x0
+
+
 def masked_blend(x, x0, noise, mask, coef, out=None):
     """Inpainting blend out = m x + (1 - m) (ca x0 + cn noise) with coef = device fp32 {ca, cn} (a row of
     ddim.inpaint_blend_table).  x, x0, noise: [B, C, *spatial]; mask: [Bm, 1, *spatial] or [Bm, *spatial] with Bm = 1 or
@@ -1447,7 +1490,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
