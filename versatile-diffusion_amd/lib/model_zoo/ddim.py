@@ -20,7 +20,7 @@ import torch
 from vd_hip import ops
 
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import capture_stream, kv_mark_stale, kv_refresh, kv_refreshable
+from .vd import DeepCache, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -54,6 +54,23 @@ def _inpaint_args(x_info, shape):
     if mask.shape[0] not in (1, shape[0]):
         raise ValueError("inpaint_mask has batch %d, expected 1 or %d" % (mask.shape[0], shape[0]))
     return True
+
+
+def _cache_args(x_info, model):
+    """(interval N, depth k) of DeepCache sampling from x_info's extension keys cache_interval (an int >= 1, default 1 = off) and
+    cache_depth (an int in [1, n - 1] for the n skips of the data net, default 1; vd.deep_cut), validated: ValueError for
+    anything else, and for N > 1 on a flow other than the 2-D image flow.  Step i of a call (sampling order, 0 = the first step
+    the call runs) is a full forward that stores the deep feature iff i % N == 0; the others reuse it.  Touches no device."""
+    N, k = x_info.get("cache_interval", 1), x_info.get("cache_depth", 1)
+    for name, v in (("cache_interval", N), ("cache_depth", k)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("x_info[%r] must be an int >= 1, got %r" % (name, v))
+    N, k = int(N), int(k)
+    if N > 1 and x_info.get("type") != "image":
+        raise ValueError("cache_interval > 1 applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if x_info.get("type") == "image" and (N > 1 or k > 1):
+        deep_cut(model.diffuser[x_info["type"]], k)        # raises for a depth out of range
+    return N, k
 
 
 def cfg_guided_eps(eps, scale):
@@ -150,7 +167,8 @@ class DDIMSampler(object):
         setattr(self, name, attr)
 
     def release_graphs(self):
-        """Drop the kept step graphs with their static latent / context / K-V buffers and private memory pools (up to two
+        """Drop the kept step graphs with their static latent / context / K-V buffers (and the kept deep feature of DeepCache
+        sampling) and private memory pools (up to two
         geometries are kept alive per sampler; at 768x768, batch 32 that is a sizeable HBM reservation).  The next
         sample() call captures again.  Serialised with running sample() calls by the sampler's lock."""
         with self._lock:
@@ -205,6 +223,7 @@ class DDIMSampler(object):
 
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
         masked = _inpaint_args(x_info, shape)
+        interval, depth = _cache_args(x_info, self.model)
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
         # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
@@ -226,9 +245,10 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint, phi)
+                                                 inpaint, phi, interval, depth)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
+            deep = DeepCache(depth) if interval > 1 else None
             if phi > 0.:
                 intermediates["guidance_rescale"] = []
             for ci in c_info_list:
@@ -237,7 +257,8 @@ class DDIMSampler(object):
             for i, step in enumerate(np.flip(timesteps)):
                 index = total_steps - i - 1
                 x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
-                                              noise_dropout=noise_dropout, rescale=rescale)
+                                              noise_dropout=noise_dropout, rescale=rescale,
+                                              deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"))
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
@@ -245,6 +266,8 @@ class DDIMSampler(object):
                     intermediates["pred_x0"].append(pred_x0.to(dtype))
                     if kfac is not None:
                         intermediates["guidance_rescale"].append(kfac)
+        if interval > 1:
+            intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
 
@@ -289,12 +312,15 @@ class DDIMSampler(object):
             ci["c"] = c.to(self.model.device)
         return copies, guided, scale, phi
 
-    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None):
+    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
-        so the data blocks in front of the first context block run once (extension key of this package's apply_model*)."""
+        so the data blocks in front of the first context block run once (extension key of this package's apply_model*).
+        deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache')."""
         xi = {"type": x_info["type"], "x": x, "repeat": 2 if guided else 1}
         if emb_rows is not None:
             xi["emb_rows"] = emb_rows
+        if deep is not None:
+            xi["deep_cache"] = deep
         if single:
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
@@ -311,11 +337,12 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0.):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
         projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
         rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
-        (fp32 [B], written by every step); and the graph."""
+        (fp32 [B], written by every step); and the graph.  cache_depth > 0 (DeepCache sampling): "graph" is the full step that
+        stores the deep feature, "graph_shallow" the step that reuses it, and "deep" holds the one kept buffer both read."""
         nb = (2 if guided else 1) * x.shape[0]
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
@@ -323,6 +350,8 @@ class DDIMSampler(object):
               "c": [torch.empty(ci["c"].shape, device=x.device, dtype=torch.float16) for ci in c_info_list],
               "kv": [dict() for _ in c_info_list], "graph": None}
         st.update(self._extra_static(x))
+        if cache_depth > 0:
+            st.update(graph_shallow=None, deep=DeepCache(cache_depth))
         if rescale > 0.:
             st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
                       kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
@@ -331,7 +360,7 @@ class DDIMSampler(object):
                       blend=torch.empty((2,), device=x.device, dtype=torch.float32))
         return st
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0.):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -345,16 +374,18 @@ class DDIMSampler(object):
         # without it computes the embedding inside the step -- replaying either under the other setting would be silently wrong;
         # so is inpainting with its mask batch: a graph captured with the blend reads the static x0 / noise / mask buffers;
         # and the guidance rescale (`rescale`: its weight), on or off whatever the positive weight: a graph captured with it
-        # launches the factor kernel and the rescaled update, one captured without it must keep giving the unrescaled bits)
+        # launches the factor kernel and the rescaled update, one captured without it must keep giving the unrescaled bits;
+        # and DeepCache sampling with its depth (0: off), not its interval: one pair of graphs serves every interval >= 2, and
+        # an uncached call never replays a graph that stores)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
-               inpaint is not None, mask_batch, rescale > 0.)
+               inpaint is not None, mask_batch, rescale > 0., cache_depth)
         st = self._static.pop(key, None)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint, rescale)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth)
         self._static[key] = st                                 # most recently used last
         return st
 
@@ -392,32 +423,42 @@ class DDIMSampler(object):
             # the kept graph was captured with / without the hoisted embedding row and this call has it the other way round
             # (precompute_step_emb started / stopped returning a table): capture again instead of replaying stale conditioning
             st["graph"] = None
+            if "graph_shallow" in st:
+                st["graph_shallow"] = None
         if pre is None:
             return None, None
         emb_tab, layout = pre
         if "embrow" not in st or st["embrow"].numel() != emb_tab.shape[1]:
-            assert st["graph"] is None, "the kept step graph reads another time-embedding buffer"
+            assert st["graph"] is None and st.get("graph_shallow") is None, "the kept step graph reads another time-embedding buffer"
             st["embrow"] = torch.empty((emb_tab.shape[1],), device=emb_tab.device, dtype=torch.float16)
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
     def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
-                     phi=0.):
+                     phi=0., interval=1, depth=1):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
-        sample() calls of the same geometry.  Returns (final fp16 latent, intermediates)."""
+        sample() calls of the same geometry.  Returns (final fp16 latent, intermediates).
+        interval > 1 (DeepCache sampling, _cache_args): step i is full iff i % interval == 0 and runs the graph st["graph"]
+        (forward that stores the deep feature + update), every other step runs st["graph_shallow"] (forward that reuses it +
+        update); each is captured the first time its kind of step is met behind step 0, which is full and, when eager, fills
+        every cache either walk needs (the shallow walk runs a subset of the full walk's blocks at the same shapes)."""
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
-        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale))
+        cache_depth = depth if interval > 1 else 0
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth))
         replay_first = self._load_state(st, x, c_info_list, inpaint, rescale)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
         steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
         emb_tab, emb_rows = self._step_emb(st, x_info, steps_dev, single)
 
-        def body():
-            eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows)
+        def body(mode=None):
+            eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows,
+                            None if mode is None else (st["deep"], mode))
             self._update_static(st, eps.contiguous(), guided)
+
+        bodies = {"graph": body if interval == 1 else (lambda: body("store")), "graph_shallow": lambda: body("reuse")}
 
         # RNG contract: the reference draws noise_like(x) = torch.randn_like(x) on every step even when sigma = 0
         # (ddim.py:167 / :294 there), so the device generator ends a sample() call advanced by one latent-sized draw per
@@ -440,16 +481,17 @@ class DDIMSampler(object):
                 st["blend"].copy_(inpaint["table"][index])
             if emb_tab is not None:
                 st["embrow"].copy_(emb_tab[i])
+            kind = "graph" if i % interval == 0 else "graph_shallow"
             if (i == 0 and not replay_first) or not self.use_graph:
-                body()
+                bodies[kind]()
             else:
-                if st["graph"] is None:
-                    st["graph"] = self._capture(body)
+                if st[kind] is None:
+                    st[kind] = self._capture(bodies[kind])
                     st["graph_embrow"] = emb_tab is not None
-                if st["graph"] is None:
-                    body()
+                if st[kind] is None:
+                    bodies[kind]()
                 else:
-                    st["graph"].replay()
+                    st[kind].replay()
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates["pred_xt"].append(st["xs"].to(dtype).clone())
                 intermediates["pred_x0"].append(st["p0"].to(dtype).clone())
@@ -513,11 +555,12 @@ class DDIMSampler(object):
             self.use_graph = False
             return None
 
-    def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None):
+    def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None,
+              deep=None):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
-        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars."""
+        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep: _eps's."""
         t_in = torch.full(((2 if guided else 1) * x.shape[0],), step, device=x.device, dtype=torch.long)
-        eps = self._eps(x_info, x, t_in, c_info_list, guided, single)
+        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep)
         sigma = float(self.ddim_sigmas[index])
         # drawn on every step like the reference's noise_like(x) (ddim.py:167 there): same generator consumption, and for
         # eta > 0 the same noise values as a reference running in fp16 on this device
@@ -562,6 +605,8 @@ class DDIMSampler(object):
     def _p_sample(self, x_info, c_info_list, t, index, repeat_noise, use_original_steps, noise_dropout, temperature, single):
         if x_info.get("inpaint_mask") is not None:
             raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")
+        if _cache_args(x_info, self.model)[0] > 1:
+            raise ValueError("cache_interval > 1: DeepCache sampling runs whole sample() loops; p_sample_ddim* keeps no feature")
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list)
         x = x_info["x"]

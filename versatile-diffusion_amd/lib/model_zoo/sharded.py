@@ -91,7 +91,8 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 
 
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
-                      images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.):
+                      images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
+                      cache_interval=1, cache_depth=1):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -104,7 +105,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
     x0 is encoded as above also when fidelity == 0, and then the full schedule runs from x_T.
 
     guidance_rescale: the samplers' c_info['guidance_rescale'] (ddim.cfg_rescale_factors), set next to the scale; a sample's
-    factors do not depend on the rank or the slice it runs in."""
+    factors do not depend on the rank or the slice it runs in.
+
+    cache_interval, cache_depth: the samplers' x_info['cache_interval'] / ['cache_depth'] (DeepCache sampling, ddim._cache_args;
+    1 = off).  The full / shallow schedule depends on the step number alone, so it is the same on every rank."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
 
@@ -133,6 +137,7 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                                                      factor=images.shape[-1] // shape[-1])
         else:
             x_info = {"type": "image", "xt": x_T}
+        x_info["cache_interval"], x_info["cache_depth"] = cache_interval, cache_depth
         from .dpm_solver import DPMSolverSDESampler
         if isinstance(sampler, DPMSolverSDESampler):
             world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -182,7 +182,77 @@ def kv_refresh(cache, c):
     cache[_KV_STALE] = set()
 
 
-def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None):
+# ---- DeepCache (x_info['deep_cache']): reuse the deep features of the previous full forward ------------------------------------
+# Ma, Fang, Wang, "DeepCache: Accelerating Diffusion Models for Free" (CVPR 2024).  A forward in "store" mode is today's forward
+# plus one side copy of the tensor that enters the last `depth` skip loads; a forward in "reuse" mode runs only the blocks in front
+# of the first `depth` saves and behind those loads, and reads that copy in place of everything in between.
+_SAVES, _LOADS = ("save", "save_hidden_feature"), ("load", "load_hidden_feature")
+
+
+def deep_cut(net, depth):
+    """(a, b) of the cached walk at `depth` for a 2-D data net (or its flat i_order + m_order + o_order list).  With S / L the
+    positions of the n saves / loads of the walk: a = S[depth - 1] + 1, so steps[0:a] ends with the depth-th save, and
+    b = L[n - depth], so steps[b:] begins with the depth-th load from the end and pops exactly those `depth` skips, last in first
+    out.  The stored feature is the tensor about to enter steps[b] (in front of the load's concat).  ValueError unless
+    1 <= depth <= n - 1 and the net is 2-D: the 0-D text flow has nothing deep to skip."""
+    if isinstance(net, (list, tuple)):
+        order = list(net)
+    else:
+        from .openaimodel import UNetModel0D_Next
+        if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("i_order", "m_order", "o_order")):
+            raise ValueError("deep_cut: DeepCache needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+        order = list(net.i_order) + list(net.m_order) + list(net.o_order)
+    S = [i for i, s in enumerate(order) if s in _SAVES]
+    L = [i for i, s in enumerate(order) if s in _LOADS]
+    n = len(S)
+    if len(L) != n:
+        raise ValueError("deep_cut: the walk has %d saves and %d loads" % (n, len(L)))
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= n - 1:
+        raise ValueError("deep_cut: depth must be an int in [1, %d], got %r" % (n - 1, depth))
+    return S[int(depth) - 1] + 1, L[n - int(depth)]
+
+
+class DeepCache(object):
+    """What x_info['deep_cache'] = (cache, "store" | "reuse") hands from a full forward to the shallow ones behind it: the depth
+    of the cut and the kept feature (channels-last fp16, all repeat * B rows; allocated by the first "store" forward, which must
+    run outside graph capture -- a captured forward only ever dereferences that one buffer)."""
+
+    def __init__(self, depth=1):
+        self.depth = depth
+        self.buf = None
+        self.key = None     # (data net, depth) of the forward that filled buf
+
+    def store(self, h, key):
+        if self.buf is None or self.buf.shape != h.shape or self.buf.device != h.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("deep_cache: the kept buffer must exist before a 'store' forward is captured into a graph")
+            self.buf = torch.empty(h.shape, device=h.device, dtype=h.dtype)
+        self.buf.copy_(h)
+        self.key = key
+
+    def load(self, key, like):
+        """The kept feature for a walk whose innermost kept skip is `like` (the tensor the first load concatenates it with)."""
+        if self.buf is None or self.key != key:
+            raise ValueError("deep_cache: 'reuse' needs a 'store' forward of the same net at the same depth first")
+        if self.buf.shape[:-1] != like.shape[:-1] or self.buf.device != like.device:
+            raise ValueError("deep_cache: the kept feature has shape %s, this forward needs %s + channels"
+                             % (tuple(self.buf.shape), tuple(like.shape[:-1])))
+        return self.buf
+
+
+def _deep_arg(x_info):
+    """x_info['deep_cache'] validated: None, or (DeepCache, "store" | "reuse") on the 2-D image flow."""
+    deep = x_info.get("deep_cache")
+    if deep is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("deep_cache applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if not (isinstance(deep, (tuple, list)) and len(deep) == 2 and isinstance(deep[0], DeepCache) and deep[1] in ("store", "reuse")):
+        raise ValueError("x_info['deep_cache'] must be (DeepCache, 'store' | 'reuse'), got %r" % (deep,))
+    return deep[0], deep[1]
+
+
+def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -194,7 +264,15 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     type that is INSIDE the first context block, behind its self-attention (CFG_HEAD_SHARE): the block takes h un-replicated and
     returns all repeat * B samples; with several types h is replicated in front of the block.
     emb_rows: {data block index: [Cout] fp16} complete first-conv bias vectors of the ResBlocks for the ONE timestep the whole
-    batch shares (VD_v2_0.precompute_step_emb); emb_silu may then be None."""
+    batch shares (VD_v2_0.precompute_step_emb); emb_silu may then be None.
+    deep: None, or (DeepCache, "store" | "reuse") with (a, b) = deep_cut(data_net, cache.depth).  "store": steps[0:b], a side
+    copy of h into the cache, steps[b:] -- the eps of the plain forward, bit for bit.  "reuse": steps[0:a] for its skips (its h
+    is dropped), h = the kept feature, steps[b:]."""
+    cut = None
+    if deep is not None:
+        if x.dim() != 4:
+            raise ValueError("deep_cache needs a 2-D data net (x_info['type'] == 'image')")
+        cut = deep_cut(data_net, deep[0].depth)
     d_iter = iter(enumerate(data_net.data_blocks))
     if emb_rows is not None:
         emb_outs = {}
@@ -279,14 +357,16 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     # LayerNorm row statistics accumulated by producer epilogues live in one arena per forward, zeroed by ONE fill
     # (the arena object is per CALL -- two threads running forwards of one net must not hand out overlapping slices -- the module
     # remembers only how many rows the previous forward took)
-    arena = ops.RowSumArena(data_net.__dict__.get("_vd_rowsum_need", 0))
+    # (a shallow forward takes less than a full one and the two alternate: one remembered value per kind of forward)
+    need_key = "_vd_rowsum_need" if deep is None or deep[1] == "store" else "_vd_rowsum_need_reuse%d" % deep[0].depth
+    arena = ops.RowSumArena(data_net.__dict__.get(need_key, 0))
     arena.begin(x.device)
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
-                              h, nb, shared, repeat)
+                              h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)))
     finally:
         arena.end()
-        data_net.__dict__["_vd_rowsum_need"] = arena.need
+        data_net.__dict__[need_key] = arena.need
 
 
 def _shares_cfg_head(module):
@@ -323,7 +403,8 @@ def _fork_region(steps, hw0, thr):
     return (a, b) if depth == 0 and any(st[0] == "c" for st in steps[a:b]) else None
 
 
-def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat):
+def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None):
+    """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk."""
     state = {"shared": shared}
 
     def walk(lo, hi, h, hs, sl=None):
@@ -362,14 +443,17 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
     region = None
     if BATCH_FORK != "0" and h.is_cuda and h.dim() == 4 and all(len(st[1]) == 1 for st in steps if st[0] == "c"):
         region = _fork_region(steps, h.shape[-2] * h.shape[-1], BATCH_FORK_HW)
-    if region is None:
-        h = walk(0, len(steps), h, hs)
-    else:
+
+    def span(lo, hi, h):
+        """steps[lo:hi] on the whole batch; the half-batch fork region is forked where it lies wholly inside the span (a cached
+        walk that is cut inside the region walks it unforked)."""
+        if region is None or not (lo <= region[0] and region[1] <= hi):
+            return walk(lo, hi, h, hs)
         a, b = region
-        h = walk(0, a, h, hs)
+        h = walk(lo, a, h, hs)
         B = h.shape[0]
         if state["shared"] or B < 2 or B % 2 or (BATCH_FORK != "1" and B < BATCH_FORK_MIN):
-            h = walk(a, len(steps), h, hs)
+            return walk(a, hi, h, hs)
         else:
             # two half-batch branches: samples 0 .. B/2 - 1 on the current stream, the rest on a side stream (inside the sampler's
             # HIP graph: parallel branches).  Batch slices of channels-last tensors are contiguous views; the region's skip tensors
@@ -397,7 +481,22 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
             h1.record_stream(main)
             main.wait_event(done)
             h = torch.cat([h0, h1], 0)
-            h = walk(b, len(steps), h, hs)
+            return walk(b, hi, h, hs)
+
+    if deep is None:
+        h = span(0, len(steps), h)
+    else:
+        cache, mode, (a, b), key = deep
+        if mode == "store":
+            h = span(0, b, h)
+            cache.store(h, key)     # a side copy: h itself goes on, so the eps is the plain forward's
+        else:
+            span(0, a, h)           # for its skips alone
+            if state["shared"]:     # no context block in front of the cut: the replicas diverge at the jump
+                hs[:] = [ops.repeat_batch(t, repeat) for t in hs]
+                state["shared"] = False
+            h = cache.load(key, hs[-1])   # (a copy carries no producer statistics: the consuming GroupNorm measures it)
+        h = span(b, len(steps), h)
     assert not state["shared"], "run_unet(repeat > 1) needs a context block in the input or middle stage"
     return h if h.dim() == 2 else ops.nhwc_to_nchw(h)   # 0-D (text-latent) data flow ends in [B, D]
 
@@ -554,10 +653,11 @@ class VD_v2_0(nn.Module):
         c_type, c = c_info["type"], c_info["c"]
         glayer_ptr = x_type if self.global_layer_ptr is None else self.global_layer_ptr
         rows = x_info.get("emb_rows")   # extension key: the t-only part precomputed for a batch that shares its timestep
+        deep = _deep_arg(x_info)        # extension key: (DeepCache, "store" | "reuse"), see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows).to(x.dtype)
+                        emb_rows=rows, deep=deep).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -565,9 +665,10 @@ class VD_v2_0(nn.Module):
         x_type, x = x_info["type"], x_info["x"]
         assert mixing_type in ("attention", "layer")
         rows = x_info.get("emb_rows")
+        deep = _deep_arg(x_info)
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
         specs = [(self.diffuser[ci["type"]].context_blocks, self._prep(ci["c"]), ci["ratio"], ci.get("kv_cache"))
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
-                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows).to(x.dtype)
+                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep).to(x.dtype)
