@@ -571,6 +571,38 @@ int vd_cfg_unipc_step_dev_rs_f16(const void* x, const void* eps, float* x_last, 
 int vd_masked_blend_f16(const void* x, const void* x0, const void* noise, const void* mask, void* out, int B, int C,
                         int64_t HW, int Bm, const float* coef, hipStream_t stream);
 
+/* Windowed (MultiDiffusion, Bar-Tal et al. 2023) sampling: every step runs the UNet on overlapping windows of the canvas latent
+ * and fuses the windows' predictions (not in the reference; tables: lib/model_zoo/windows.py).
+ *
+ * vd_window_gather_f16 cuts the windows: x fp16 [B, C, H, W] -> win fp16 [B, slots, C, h, w],
+ *   win[b, k, c, i, j] = x[b, c, oy_k + i, ox_k + j],  the column (ox_k + j) % W when wrap != 0,
+ * with offs = int32 [slots][2] rows {oy_k, ox_k} in DEVICE memory.  The copy is bit-exact: 16-byte accesses where a row segment
+ * of 8 elements is whole, does not cross the wrap seam and is 16-byte aligned on both sides, else 2-byte accesses of the same
+ * elements.
+ *
+ * vd_window_merge_f16 fuses them: eps_win fp16 [RB, slots, C, h, w] (the UNet's output for one chunk of windows; RB = the
+ * [uncond ; cond] rows), acc fp32 [RB, C, H, W], eps fp16 [RB, C, H, W], wgt fp32 [h, w], inv_den fp32 [H, W].  One thread
+ * owns one canvas element (rb, c, Y, X) -- a gather: no atomics, a fixed order:
+ *   a = first ? 0 : acc[...]
+ *   for k = 0 .. valid-1 ascending, if window k covers the pixel at (i, j) = (Y - oy_k, X - ox_k [mod W when wrap]):
+ *       a = fmaf(wgt[i, j], (float)eps_win[rb, k, c, i, j], a)
+ *   acc[...] = a  unless first && last
+ *   if last: eps[...] = fp16(a * inv_den[Y, X])     one fp32 multiply, then one rounding to fp16
+ * Slots >= valid are never read (the padded slots of a call's last chunk).  acc may be NULL only when first && last; eps is
+ * written only when last (and may be NULL otherwise).  The chain runs in ascending window order and acc is exact fp32 between
+ * launches, so the result has the same bits however the windows are split into launches.
+ *
+ * Both neither allocate nor synchronise (capturable).  They return < 0 (vd_last_error) for null pointers, non-positive sizes,
+ * h > H or w > W, and the merge for valid outside [1, slots].  The offsets live in device memory and are NOT validated by
+ * these entry points: callers pass tables built by windows.window_offsets (0 <= oy <= H - h; 0 <= ox <= W - w, or 0 <= ox < W
+ * when wrapping).  Neither kernel leaves its buffers for another table -- the gather brings an offset outside that range back
+ * into it, the merge tests coverage from the pixel's side -- but what they then compute is unspecified. */
+int vd_window_gather_f16(const void* x, void* win, const int32_t* offs, int B, int C, int H, int W, int h, int w, int slots,
+                         int wrap, hipStream_t stream);
+int vd_window_merge_f16(const void* eps_win, float* acc, void* eps, const float* wgt, const float* inv_den,
+                        const int32_t* offs, int RB, int C, int H, int W, int h, int w, int slots, int valid, int wrap,
+                        int first, int last, hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

@@ -19,6 +19,7 @@ import torch
 
 from vd_hip import ops
 
+from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
 from .vd import DeepCache, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
 
@@ -71,6 +72,42 @@ def _cache_args(x_info, model):
     if x_info.get("type") == "image" and (N > 1 or k > 1):
         deep_cut(model.diffuser[x_info["type"]], k)        # raises for a depth out of range
     return N, k
+
+
+def _window_args(x_info, shape, model):
+    """The plan of a windowed (MultiDiffusion) call from x_info's extension keys, or None: `window` (an int or (h, w) in latent
+    pixels; absent = off), `window_stride` (an int or a pair, default half the window per axis), `window_wrap` (bool, default
+    False: the x axis wraps around, a 360-degree panorama), `window_weight` ('uniform', the default, or 'gaussian') and
+    `window_batch` (an int >= 1, default 8: the most windows per sample in one UNet forward).  Validated with the tables of
+    lib/model_zoo/windows.py: ValueError for a bad value of any key and for a flow other than the 2-D image flow.  None also
+    when the plan has a single window (window == canvas): that call is the plain call and gives its bits.  The plan: the
+    geometry "key" (h, w, sy, sx, wrap, weight, nc, m), "n" windows run as "nc" forwards of "m" slots per sample, "offsets"
+    int32 [nc, m, 2] (the unused slots of the last forward repeat the last window), "wgt" fp32 [h, w] and "inv_den" fp32
+    [H, W].  Touches no device."""
+    window = x_info.get("window")
+    if window is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("window applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4:
+        raise ValueError("window: the latent shape must be [B, C, H, W], got %s" % (shape,))
+    H, W = shape[2:]
+    h, w = windows.int_pair("window", window)
+    stride = x_info.get("window_stride")
+    sy, sx = (max(h // 2, 1), max(w // 2, 1)) if stride is None else windows.int_pair("window_stride", stride)
+    wrap, weight = x_info.get("window_wrap", False), x_info.get("window_weight", "uniform")
+    from .openaimodel import Downsample
+    factor = 2 ** sum(isinstance(mod, Downsample) for mod in model.diffuser[x_info["type"]].modules())
+    offsets = windows.window_offsets(H, W, (h, w), (sy, sx), wrap, multiple=factor)
+    wgt = windows.window_weights(h, w, weight)
+    n = offsets.shape[0]
+    nc, m = windows.window_chunks(n, x_info.get("window_batch", 8))
+    if n == 1:
+        return None
+    padded = np.concatenate([offsets, np.repeat(offsets[-1:], nc * m - n, axis=0)]).reshape(nc, m, 2)
+    return {"key": (h, w, sy, sx, bool(wrap), weight, nc, m), "n": n, "nc": nc, "m": m, "offsets": np.ascontiguousarray(padded),
+            "wgt": wgt, "inv_den": windows.window_inv_den(H, W, offsets, wgt, bool(wrap))}
 
 
 def cfg_guided_eps(eps, scale):
@@ -168,7 +205,7 @@ class DDIMSampler(object):
 
     def release_graphs(self):
         """Drop the kept step graphs with their static latent / context / K-V buffers (and the kept deep feature of DeepCache
-        sampling) and private memory pools (up to two
+        sampling, the tables and buffers of windowed sampling) and private memory pools (up to two
         geometries are kept alive per sampler; at 768x768, batch 32 that is a sizeable HBM reservation).  The next
         sample() call captures again.  Serialised with running sample() calls by the sampler's lock."""
         with self._lock:
@@ -224,10 +261,13 @@ class DDIMSampler(object):
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
         masked = _inpaint_args(x_info, shape)
         interval, depth = _cache_args(x_info, self.model)
+        window = _window_args(x_info, shape, self.model)
+        if window is not None and interval > 1:
+            raise ValueError("cache_interval > 1 does not combine with window: DeepCache would keep one feature per chunk of windows")
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
         # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
-        c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list)
+        c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list, 1 if window is None else window["m"])
         dtype = c_info_list[0]["conditioning"].dtype
         x_info["x"], timesteps, blend_noise = self._start_latent(shape, x_info, masked, device, dtype)
         inpaint = None
@@ -245,10 +285,11 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint, phi, interval, depth)
+                                                 inpaint, phi, interval, depth, window)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
             deep = DeepCache(depth) if interval > 1 else None
+            wstate = None if window is None else self._window_state(window, x, guided)      # once per call
             if phi > 0.:
                 intermediates["guidance_rescale"] = []
             for ci in c_info_list:
@@ -258,7 +299,8 @@ class DDIMSampler(object):
                 index = total_steps - i - 1
                 x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                               noise_dropout=noise_dropout, rescale=rescale,
-                                              deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"))
+                                              deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"),
+                                              window=wstate)
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
@@ -292,12 +334,13 @@ class DDIMSampler(object):
             x = torch.randn(shape, device=device, dtype=dtype)
         return x, timesteps, x if noise is None else noise
 
-    def _cfg_contexts(self, c_info_list):
+    def _cfg_contexts(self, c_info_list, slots=1):
         """(copies, guided, scale, phi): shallow copies of the contexts with 'c', the batch the UNet sees ([uncond ; cond] under
         guidance), on the model's device.  The samplers work on the copies: 'c' (possibly a static buffer the captured graph
         reads) and 'kv_cache' never appear in the caller's dicts.  phi = c_info['guidance_rescale'] (extension key, default
         0 = off; cfg_rescale_factors): ValueError unless it is a real number in [0, 1] that all contexts agree on; an unguided
-        call (scale == 1) ignores it, phi = 0."""
+        call (scale == 1) ignores it, phi = 0.  slots > 1 (windowed sampling, the plan's m): the UNet's batch order is
+        (replica, sample, window slot), so every row is repeated `slots` times in place."""
         scale = c_info_list[0]["unconditional_guidance_scale"]
         for ci in c_info_list:
             assert ci["unconditional_guidance_scale"] == scale, \
@@ -308,14 +351,52 @@ class DDIMSampler(object):
             phi = 0.
         copies = [dict(ci) for ci in c_info_list]
         for ci in copies:
-            c = torch.cat([ci["unconditional_conditioning"], ci["conditioning"]]) if guided else ci["conditioning"]
+            parts = [ci["unconditional_conditioning"], ci["conditioning"]] if guided else [ci["conditioning"]]
+            if slots > 1:
+                parts = [p.repeat_interleave(slots, 0) for p in parts]
+            c = torch.cat(parts) if guided else parts[0]
             ci["c"] = c.to(self.model.device)
         return copies, guided, scale, phi
 
-    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None):
+    @staticmethod
+    def _window_state(plan, x, guided):
+        """The device side of a windowed call's plan (_window_args) for the canvas latent x [B, C, H, W]: the tables "offs"
+        (int32 [nc, m, 2]), "wgt", "inv_den", and the buffers "win" (fp16 [B, m, C, h, w], the UNet's input), "acc" (fp32
+        canvas, only with several forwards per step) and "eps" (fp16 [R B, C, H, W], what _eps returns).  Lives in the static
+        state entry, or for one call of the eager loop."""
+        h, w = plan["key"][:2]
+        B, C, H, W = x.shape
+        rb = (2 if guided else 1) * B
+        dev = dict(device=x.device)
+        return {"plan": plan, "offs": torch.from_numpy(plan["offsets"]).to(**dev), "wgt": torch.from_numpy(plan["wgt"]).to(**dev),
+                "inv_den": torch.from_numpy(plan["inv_den"]).to(**dev),
+                "win": torch.empty((B, plan["m"], C, h, w), dtype=torch.float16, **dev),
+                "acc": torch.empty((rb, C, H, W), dtype=torch.float32, **dev) if plan["nc"] > 1 else None,
+                "eps": torch.empty((rb, C, H, W), dtype=torch.float16, **dev)}
+
+    def _eps_windowed(self, x_info, x, t, c_info_list, guided, single, emb_rows, ws):
+        """The canvas prediction [R B, C, H, W] of a windowed step: per chunk of the plan, in order, ops.window_gather of the
+        latent's windows, the UNet on them as a batch of B m samples (t and the contexts carry R B m rows, order (r, b, k)),
+        and ops.window_merge of what it predicts -- a sum in ascending window order, so the chunking does not decide a bit."""
+        plan = ws["plan"]
+        (h, w, _, _, wrap), nc, m = plan["key"][:5], plan["nc"], plan["m"]
+        x = x.to(torch.float16).contiguous()
+        B, C, H, W = x.shape
+        for k in range(nc):
+            ops.window_gather(x, ws["offs"][k], h, w, wrap, out=ws["win"])
+            e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list, guided, single, emb_rows)
+            ops.window_merge(e.to(torch.float16).contiguous().view(-1, m, C, h, w), ws["offs"][k], ws["wgt"], ws["inv_den"], H, W,
+                             min(m, plan["n"] - k * m), wrap, k == 0, k == nc - 1, acc=ws["acc"], out=ws["eps"])
+        return ws["eps"]
+
+    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None, window=None):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
         so the data blocks in front of the first context block run once (extension key of this package's apply_model*).
-        deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache')."""
+        deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache').
+        window: the _window_state of a windowed call -- x is the canvas, and so is what comes back (_eps_windowed)."""
+        if window is not None:
+            assert deep is None, "DeepCache does not combine with windows"
+            return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window)
         xi = {"type": x_info["type"], "x": x, "repeat": 2 if guided else 1}
         if emb_rows is not None:
             xi["emb_rows"] = emb_rows
@@ -337,13 +418,15 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
         projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
         rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
         (fp32 [B], written by every step); and the graph.  cache_depth > 0 (DeepCache sampling): "graph" is the full step that
-        stores the deep feature, "graph_shallow" the step that reuses it, and "deep" holds the one kept buffer both read."""
-        nb = (2 if guided else 1) * x.shape[0]
+        stores the deep feature, "graph_shallow" the step that reuses it, and "deep" holds the one kept buffer both read.
+        window (the plan of _window_args): "window" holds its tables and buffers (_window_state), and "ts" has a row per
+        window slot like the context batches."""
+        nb = (2 if guided else 1) * x.shape[0] * (1 if window is None else window["m"])
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
               "coef": torch.empty((self.coef_width,), device=x.device, dtype=torch.float32),
@@ -352,6 +435,8 @@ class DDIMSampler(object):
         st.update(self._extra_static(x))
         if cache_depth > 0:
             st.update(graph_shallow=None, deep=DeepCache(cache_depth))
+        if window is not None:
+            st["window"] = self._window_state(window, x, guided)
         if rescale > 0.:
             st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
                       kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
@@ -360,7 +445,7 @@ class DDIMSampler(object):
                       blend=torch.empty((2,), device=x.device, dtype=torch.float32))
         return st
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -376,16 +461,18 @@ class DDIMSampler(object):
         # and the guidance rescale (`rescale`: its weight), on or off whatever the positive weight: a graph captured with it
         # launches the factor kernel and the rescaled update, one captured without it must keep giving the unrescaled bits;
         # and DeepCache sampling with its depth (0: off), not its interval: one pair of graphs serves every interval >= 2, and
-        # an uncached call never replays a graph that stores)
+        # an uncached call never replays a graph that stores;
+        # and windowed sampling with its whole geometry (h, w, sy, sx, wrap, weight, nc, m), None when off: the graph holds the
+        # gather / forward / merge chain of that plan and reads its tables)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
-               inpaint is not None, mask_batch, rescale > 0., cache_depth)
+               inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"])
         st = self._static.pop(key, None)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window)
         self._static[key] = st                                 # most recently used last
         return st
 
@@ -434,19 +521,21 @@ class DDIMSampler(object):
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
     def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
-                     phi=0., interval=1, depth=1):
+                     phi=0., interval=1, depth=1, window=None):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry.  Returns (final fp16 latent, intermediates).
         interval > 1 (DeepCache sampling, _cache_args): step i is full iff i % interval == 0 and runs the graph st["graph"]
         (forward that stores the deep feature + update), every other step runs st["graph_shallow"] (forward that reuses it +
         update); each is captured the first time its kind of step is met behind step 0, which is full and, when eager, fills
-        every cache either walk needs (the shallow walk runs a subset of the full walk's blocks at the same shapes)."""
+        every cache either walk needs (the shallow walk runs a subset of the full walk's blocks at the same shapes).
+        window (the plan of _window_args): the step's prediction is the fusion of the windows' (_eps_windowed); the update, the
+        rescale factors, the blend, the seeded noise and the solver histories see the canvas and nothing else."""
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
-        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth))
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window))
         replay_first = self._load_state(st, x, c_info_list, inpaint, rescale)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
@@ -455,7 +544,7 @@ class DDIMSampler(object):
 
         def body(mode=None):
             eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows,
-                            None if mode is None else (st["deep"], mode))
+                            None if mode is None else (st["deep"], mode), st.get("window"))
             self._update_static(st, eps.contiguous(), guided)
 
         bodies = {"graph": body if interval == 1 else (lambda: body("store")), "graph_shallow": lambda: body("reuse")}
@@ -556,11 +645,12 @@ class DDIMSampler(object):
             return None
 
     def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None,
-              deep=None):
+              deep=None, window=None):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
-        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep: _eps's."""
-        t_in = torch.full(((2 if guided else 1) * x.shape[0],), step, device=x.device, dtype=torch.long)
-        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep)
+        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep, window: _eps's."""
+        rows = (2 if guided else 1) * x.shape[0] * (1 if window is None else window["plan"]["m"])
+        t_in = torch.full((rows,), step, device=x.device, dtype=torch.long)
+        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep, window=window)
         sigma = float(self.ddim_sigmas[index])
         # drawn on every step like the reference's noise_like(x) (ddim.py:167 there): same generator consumption, and for
         # eta > 0 the same noise values as a reference running in fp16 on this device
@@ -607,6 +697,8 @@ class DDIMSampler(object):
             raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")
         if _cache_args(x_info, self.model)[0] > 1:
             raise ValueError("cache_interval > 1: DeepCache sampling runs whole sample() loops; p_sample_ddim* keeps no feature")
+        if x_info.get("window") is not None:
+            raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows")
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list)
         x = x_info["x"]

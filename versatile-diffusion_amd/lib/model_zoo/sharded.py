@@ -92,7 +92,8 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
                       images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
-                      cache_interval=1, cache_depth=1):
+                      cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
+                      window_weight="uniform", window_batch=8):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -108,7 +109,11 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
     factors do not depend on the rank or the slice it runs in.
 
     cache_interval, cache_depth: the samplers' x_info['cache_interval'] / ['cache_depth'] (DeepCache sampling, ddim._cache_args;
-    1 = off).  The full / shallow schedule depends on the step number alone, so it is the same on every rank."""
+    1 = off).  The full / shallow schedule depends on the step number alone, so it is the same on every rank.
+
+    window, window_stride, window_wrap, window_weight, window_batch: the samplers' x_info keys of the same names (windowed /
+    MultiDiffusion sampling, ddim._window_args; window=None = off, and then none of them is set).  `shape` is the canvas; the
+    windows lie on the latent's H and W, so a rank's slice of the batch sees the same plan as the whole batch."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
 
@@ -138,6 +143,9 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
         else:
             x_info = {"type": "image", "xt": x_T}
         x_info["cache_interval"], x_info["cache_depth"] = cache_interval, cache_depth
+        if window is not None:
+            x_info.update(window=window, window_stride=window_stride, window_wrap=window_wrap, window_weight=window_weight,
+                          window_batch=window_batch)
         from .dpm_solver import DPMSolverSDESampler
         if isinstance(sampler, DPMSolverSDESampler):
             world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -1259,6 +1259,71 @@ def masked_blend(x, x0, noise, mask, coef, out=None):
     return out
 
 
+def _window_table(offs):
+    _req(offs, "offs", torch.int32)
+    if offs.dim() != 2 or offs.shape[1] != 2 or offs.shape[0] < 1:
+        raise VdHipError("offs has shape %s, expected [slots, 2]" % (tuple(offs.shape),))
+    return offs.shape[0]
+
+
+def window_gather(x, offs, h, w, wrap, out=None):
+    """The windows of a canvas latent (windowed sampling; contract in include/vd_hip.h): x fp16 [B, C, H, W], offs device int32
+    [slots, 2] rows (oy, ox) of windows.window_offsets -> out fp16 [B, slots, C, h, w], a bit-exact copy with the columns taken
+    modulo W when `wrap`.  The offsets are not validated (that would need a device read)."""
+    _req(x, "x")
+    slots = _window_table(offs)
+    if x.dim() != 4:
+        raise VdHipError("x has shape %s, expected [B, C, H, W]" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    h, w = int(h), int(w)
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise VdHipError("a window of %d x %d does not fit the canvas %d x %d" % (h, w, H, W))
+    if out is None:
+        out = torch.empty((B, slots, C, h, w), device=x.device, dtype=torch.float16)
+    _req(out, "out")
+    if tuple(out.shape) != (B, slots, C, h, w):
+        raise VdHipError("out has shape %s, expected %s" % (tuple(out.shape), (B, slots, C, h, w)))
+    _check(lib().vd_window_gather_f16(_ptr(x), _ptr(out), _ptr(offs), B, C, H, W, h, w, slots, int(bool(wrap)), _stream()))
+    return out
+
+
+def window_merge(eps_win, offs, wgt, inv_den, H, W, valid, wrap, first, last, acc=None, out=None):
+    """One launch of the windows' fusion (contract in include/vd_hip.h): eps_win fp16 [RB, slots, C, h, w] (a chunk of the
+    UNet's window predictions), offs device int32 [slots, 2], wgt fp32 [h, w], inv_den fp32 [H, W]; the first `valid` slots are
+    summed in ascending order onto acc (fp32 [RB, C, H, W]; started at 0 when `first`), and when `last` out (fp16
+    [RB, C, H, W]) = fp16(acc * inv_den).  acc is needed unless first and last.  Returns out when `last`, else acc."""
+    _req(eps_win, "eps_win"); _req(wgt, "wgt", torch.float32); _req(inv_den, "inv_den", torch.float32)
+    slots = _window_table(offs)
+    if eps_win.dim() != 5 or eps_win.shape[1] != slots:
+        raise VdHipError("eps_win has shape %s, expected [RB, %d, C, h, w]" % (tuple(eps_win.shape), slots))
+    RB, _, C, h, w = eps_win.shape
+    H, W, valid, first, last = int(H), int(W), int(valid), bool(first), bool(last)
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise VdHipError("a window of %d x %d does not fit the canvas %d x %d" % (h, w, H, W))
+    if tuple(wgt.shape) != (h, w):
+        raise VdHipError("wgt has shape %s, expected %s" % (tuple(wgt.shape), (h, w)))
+    if tuple(inv_den.shape) != (H, W):
+        raise VdHipError("inv_den has shape %s, expected %s" % (tuple(inv_den.shape), (H, W)))
+    if not 1 <= valid <= slots:
+        raise VdHipError("valid = %d outside [1, %d]" % (valid, slots))
+    canvas = (RB, C, H, W)
+    if acc is None and not (first and last):
+        if not first:
+            raise VdHipError("acc is needed to continue a sum (first is False)")
+        acc = torch.empty(canvas, device=eps_win.device, dtype=torch.float32)
+    _req(acc, "acc", torch.float32)
+    if acc is not None and tuple(acc.shape) != canvas:
+        raise VdHipError("acc has shape %s, expected %s" % (tuple(acc.shape), canvas))
+    if last and out is None:
+        out = torch.empty(canvas, device=eps_win.device, dtype=torch.float16)
+    _req(out, "out")
+    if out is not None and tuple(out.shape) != canvas:
+        raise VdHipError("out has shape %s, expected %s" % (tuple(out.shape), canvas))
+    _check(lib().vd_window_merge_f16(_ptr(eps_win), _ptr(acc), _ptr(out), _ptr(wgt), _ptr(inv_den), _ptr(offs), RB, C, H, W,
+                                     h, w, slots, valid, int(bool(wrap)), int(first), int(last), _stream()))
+    return out if last else acc
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1490,7 +1555,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
