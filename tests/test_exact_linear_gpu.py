@@ -5,7 +5,7 @@ slabs, the in-kernel fix-up, the reduce launch, the final fp16 rounding -- is ex
 float64 reference in every element, whatever tile shape, split factor or summation order it uses, and a dropped, duplicated or
 mislocated term changes some element by at least 1.  A failure reports the mismatching coordinates and the active override, variant
 or split (vdtest_util.exact_mismatch).  Only exact epilogues are covered (bias, row vector, residual, power-of-two alpha, two-source
-concat, folded skip convolution); activations, GEGLU and the LayerNorm fold stay with the tolerance tests of test_kernels_gpu.py.
+concat, folded skip convolution); activations, GEGLU and the LayerNorm fold are checked per element by test_exact_epilogue_gpu.py.
 """
 import pytest
 import torch

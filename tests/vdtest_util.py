@@ -338,3 +338,35 @@ def attn_mismatch(out, ref, context="", rel=ATTN_REL, win_key=None, qblock=128, 
         want = "%.10g" % refn[b, i, h, c] if lo[b, i, h, c] == hi[b, i, h, c] else "%.10g (fp16 %g..%g)" % (refn[b, i, h, c], lo[b, i, h, c], hi[b, i, h, c])
         lines.append("  (batch=%d, query=%d, head=%d, channel=%d): got %g, expected %s%s" % (b, i, h, c, got[b, i, h, c], want, sel))
     return "\n".join(lines)
+
+
+# ---- per-element checks of the fused epilogues: tests/epilogue_cases.py holds the case table -------------------------------------
+def fp16_steps(lo, hi):
+    """How many fp16 steps lie between the fp16-valued arrays lo <= hi (0: the same value; +-0 count as one value)."""
+    def key(v):
+        bits = np.asarray(v, np.float16).view(np.int16).astype(np.int64)
+        return np.where(bits < 0, -(bits & 0x7fff), bits)
+    return key(hi) - key(lo)
+
+
+def interval_mismatch(out, lo, hi, names, context="", limit=6):
+    """The acceptance rule of the interval cases: the value a kernel rounds to fp16 is known to lie between two ADJACENT fp16 values
+    (or on one), and `lo` / `hi` are those two values carried through the roundings that follow (a residual add).  An element of
+    `out` passes if it equals lo or hi -- where no rounding follows that is every fp16 value of the interval.  None when every
+    element passes, else a report in the form of exact_mismatch: count, extent per axis, the first `limit` coordinates."""
+    got = torch.as_tensor(out).detach().double().cpu().numpy()
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if got.shape != lo.shape:
+        return "%s: shape %s, expected %s" % (context, got.shape, lo.shape)
+    bad = ~((got == lo) | (got == hi))
+    if not bad.any():
+        return None
+    idx = np.argwhere(bad)
+    lines = ["%s: %d of %d elements fail" % (context, idx.shape[0], lo.size)]
+    lines.append("  extent: " + ", ".join("%s %d..%d" % (n, idx[:, i].min(), idx[:, i].max()) for i, n in enumerate(names)))
+    for c in idx[:limit].tolist():
+        where = ", ".join("%s=%d" % (n, v) for n, v in zip(names, c))
+        k = tuple(c)
+        want = "%.10g" % lo[k] if lo[k] == hi[k] else "%.10g or %.10g" % (lo[k], hi[k])
+        lines.append("  (%s): got %.10g, expected %s" % (where, got[k], want))
+    return "\n".join(lines)
