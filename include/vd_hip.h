@@ -603,6 +603,42 @@ int vd_window_merge_f16(const void* eps_win, float* acc, void* eps, const float*
                         const int32_t* offs, int RB, int C, int H, int W, int h, int w, int slots, int valid, int wrap,
                         int first, int last, hipStream_t stream);
 
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024; not in the reference) at one skip concatenation of the
+ * UNet's decoder.  The setting is four real numbers (b1, b2, s1, s2).  With W1 the width of the widest h that enters any
+ * output-stage block of the 2-D data net and W2 = W1 / 2 (integer), a skip load whose entering h [B, H, W, C0] has C0 == W1 is
+ * stage 1 and uses (b, s) = (b1, s1), C0 == W2 is stage 2 and uses (b2, s2), any other width is untouched (lib/model_zoo/vd.py:
+ * freeu_stages).  vd_freeu_f16 is one stage's work on h and the popped skip [B, H, W, C1], both channels-last fp16, in ONE launch:
+ *
+ *   backbone  h_out[..., c] = fp16(fp32(h[..., c]) * b)  for c < C0 / 2 (the product rounded to fp32, then once to fp16);
+ *             the other channels are copied bit for bit.
+ *   skip      per sample and channel, on the H x W plane x (H, W >= 2):  y = Re(ifft2(mask * fft2(x))),  mask = s on the
+ *             frequencies {-1, 0} x {-1, 0} and 1 elsewhere (diffusers' fourier_filter with threshold 1).  Written out, with
+ *             tp = 2 pi p / H and fq = 2 pi q / W:
+ *                 S0  = sum x
+ *                 Ay  = sum x cos tp          By  = sum x sin tp
+ *                 Ax  = sum x cos fq          Bx  = sum x sin fq
+ *                 Axy = sum x cos(tp + fq)    Bxy = sum x sin(tp + fq)
+ *                 y[p, q] = x[p, q] + g (S0 + Ay cos tp + By sin tp + Ax cos fq + Bx sin fq + Axy cos(tp + fq) + Bxy sin(tp + fq))
+ *                 g = (s - 1) / (H W)      formed in double from the fp32 s, rounded once to fp32
+ *
+ * Tables (DEVICE memory, fp32): cy, sy [H] = cos / sin tp;  cx, sx [W] = cos / sin fq;  cxy, sxy [H W] = cos / sin(tp + fq) at
+ * index p W + q.  There is no trig on the device: the host builds them in float64 and rounds once to fp32, with the angle
+ * reduced on integers first -- k / n of a turn with k = p mod H, q mod W, (p W + q H) mod (H W) -- and the multiples of a quarter
+ * turn set to exactly 0 or +-1 (vd_hip/ops.py: freeu_tables).
+ *
+ * Arithmetic: the seven sums are fp32 (S0 by additions, the others by one fma per pixel), in an order that depends on (H, W)
+ * alone: thread t of the 256 of a block takes pixels t, t + 256, .. ascending, a wave adds its lanes by the xor butterfly
+ * 32, 16, .. 1, the four waves are added in ascending order.  A block owns 8 channels of one sample; nothing is atomic, so a
+ * sample's output has the same bits for any batch size, batch position and run.  The bracket is S0 followed by the six fmas in
+ * the order written, y = fma(g, bracket, x) in fp32, then one rounding to fp16.
+ *
+ * h_out and skip_out are separate tensors: nothing is filtered in place (the outputs must not alias the inputs).  Neither
+ * allocates nor synchronises (capturable).  Returns < 0 (vd_last_error) for null pointers, non-positive sizes, H or W < 2, C0 or
+ * C1 not a multiple of 8, pointers that are not 16-byte aligned, aliased outputs, or b or s not finite. */
+int vd_freeu_f16(const void* h, const void* skip, void* h_out, void* skip_out, const float* cy, const float* sy, const float* cx,
+                 const float* sx, const float* cxy, const float* sxy, int B, int H, int W, int C0, int C1, float b, float s,
+                 hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

@@ -21,7 +21,7 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import DeepCache, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
+from .vd import DeepCache, _freeu_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -259,6 +259,7 @@ class DDIMSampler(object):
             return self._ddim_sampling_multicontext(shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, single)
 
     def _ddim_sampling_multicontext(self, shape, x_info, c_info_list, noise_dropout, temperature, log_every_t, _single):
+        _freeu_arg(x_info)      # x_info['freeu'] (extension key, vd.freeu_setting): a bad value raises before anything is drawn
         masked = _inpaint_args(x_info, shape)
         interval, depth = _cache_args(x_info, self.model)
         window = _window_args(x_info, shape, self.model)
@@ -393,7 +394,8 @@ class DDIMSampler(object):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
         so the data blocks in front of the first context block run once (extension key of this package's apply_model*).
         deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache').
-        window: the _window_state of a windowed call -- x is the canvas, and so is what comes back (_eps_windowed)."""
+        window: the _window_state of a windowed call -- x is the canvas, and so is what comes back (_eps_windowed).
+        x_info['freeu'] (FreeU, vd.freeu_setting) travels with every forward, so with windows it acts inside each window's."""
         if window is not None:
             assert deep is None, "DeepCache does not combine with windows"
             return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window)
@@ -402,6 +404,8 @@ class DDIMSampler(object):
             xi["emb_rows"] = emb_rows
         if deep is not None:
             xi["deep_cache"] = deep
+        if x_info.get("freeu") is not None:
+            xi["freeu"] = x_info["freeu"]
         if single:
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
@@ -445,12 +449,8 @@ class DDIMSampler(object):
                       blend=torch.empty((2,), device=x.device, dtype=torch.float32))
         return st
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None):
-        """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
-        geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
-        launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
-        if not self.graph_cache:
-            return None
+    def _static_key(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None):
+        """What a kept step graph is good for: a call with another key never replays it (_static_state)."""
         # in-place updates / load_state_dict bump a parameter's version, .half() / .to() move its storage: the key hashes the
         # ORDERED (storage, version) pairs of every parameter and buffer (an additive checksum would let two parameters
         # that swap storages collide)
@@ -463,11 +463,23 @@ class DDIMSampler(object):
         # and DeepCache sampling with its depth (0: off), not its interval: one pair of graphs serves every interval >= 2, and
         # an uncached call never replays a graph that stores;
         # and windowed sampling with its whole geometry (h, w, sy, sx, wrap, weight, nc, m), None when off: the graph holds the
-        # gather / forward / merge chain of that plan and reads its tables)
+        # gather / forward / merge chain of that plan and reads its tables;
+        # and FreeU with its four values (b1, b2, s1, s2), None when off or all ones: the scalars are arguments of the captured
+        # ops.freeu launches, and which stages launch at all depends on them -- one graph per setting)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
-               inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"])
+               inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"],
+               _freeu_arg(x_info))
+        return key
+
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None):
+        """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
+        geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
+        launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
+        if not self.graph_cache:
+            return None
+        key = self._static_key(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window)
         st = self._static.pop(key, None)
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
@@ -699,6 +711,7 @@ class DDIMSampler(object):
             raise ValueError("cache_interval > 1: DeepCache sampling runs whole sample() loops; p_sample_ddim* keeps no feature")
         if x_info.get("window") is not None:
             raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows")
+        _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list)
         x = x_info["x"]

@@ -93,7 +93,7 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
                       images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
-                      window_weight="uniform", window_batch=8):
+                      window_weight="uniform", window_batch=8, freeu=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -113,7 +113,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     window, window_stride, window_wrap, window_weight, window_batch: the samplers' x_info keys of the same names (windowed /
     MultiDiffusion sampling, ddim._window_args; window=None = off, and then none of them is set).  `shape` is the canvas; the
-    windows lie on the latent's H and W, so a rank's slice of the batch sees the same plan as the whole batch."""
+    windows lie on the latent's H and W, so a rank's slice of the batch sees the same plan as the whole batch.
+
+    freeu: the samplers' x_info['freeu'] (FreeU, vd.freeu_setting: (b1, b2, s1, s2) or a dict of them; None = off, and then the
+    key is not set).  A sample's filtered skips do not depend on the batch it runs in, so neither on the rank."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
 
@@ -146,6 +149,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
         if window is not None:
             x_info.update(window=window, window_stride=window_stride, window_wrap=window_wrap, window_weight=window_weight,
                           window_batch=window_batch)
+        if freeu is not None:
+            x_info["freeu"] = freeu
         from .dpm_solver import DPMSolverSDESampler
         if isinstance(sampler, DPMSolverSDESampler):
             world = dist.get_world_size(group) if dist.is_initialized() else 1

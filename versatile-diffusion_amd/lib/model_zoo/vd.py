@@ -252,7 +252,76 @@ def _deep_arg(x_info):
     return deep[0], deep[1]
 
 
-def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None):
+# ---- FreeU (x_info['freeu']): backbone scaling and Fourier-filtered skips at the decoder's skip loads ----------------------------
+# Si et al., "FreeU: Free Lunch in Diffusion U-Net" (CVPR 2024).  The setting is (b1, b2, s1, s2); a load whose entering h has the
+# width W1 of the widest h that enters any output-stage block is stage 1 (b1, s1), the width W1 // 2 is stage 2 (b2, s2), any other
+# load is untouched.  What a stage does to h and the popped skip: ops.freeu (contract in include/vd_hip.h).
+_FREEU_KEYS = ("b1", "b2", "s1", "s2")
+
+
+def freeu_entering_widths(model_channels, channel_mult, num_res_blocks):
+    """The width of the h that enters each output-stage block (= each skip load, in walk order) of a UNetModel2D_Next with these
+    arguments: the decoder starts at the middle block's width and every block leaves its level's width behind."""
+    mult = list(channel_mult)
+    nrb = [num_res_blocks] * len(mult) if isinstance(num_res_blocks, (int, np.integer)) else list(num_res_blocks)
+    ch, widths = int(model_channels) * int(mult[-1]), []
+    for level in reversed(range(len(mult))):
+        for _ in range(int(nrb[level]) + 1):
+            widths.append(ch)
+            ch = int(model_channels) * int(mult[level])
+    return widths
+
+
+def freeu_stages(net):
+    """(W1, W2, blocks1, blocks2) of FreeU on a 2-D data net (or on a dict of its arguments model_channels, channel_mult,
+    num_res_blocks): the two stage widths and the output-block indices of either stage.  ValueError for a net without planes."""
+    if isinstance(net, dict):
+        args = net
+    else:
+        from .openaimodel import UNetModel0D_Next
+        if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("model_channels", "channel_mult", "num_res_blocks")):
+            raise ValueError("freeu needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+        args = {k: getattr(net, k) for k in ("model_channels", "channel_mult", "num_res_blocks")}
+    widths = freeu_entering_widths(args["model_channels"], args["channel_mult"], args["num_res_blocks"])
+    W1 = max(widths)
+    W2 = W1 // 2
+    return W1, W2, [i for i, w in enumerate(widths) if w == W1], [i for i, w in enumerate(widths) if w == W2]
+
+
+def freeu_setting(value):
+    """x_info['freeu'] as (b1, b2, s1, s2) floats, or None when it is absent, None or all ones (FreeU off: today's forward).
+    Accepted: a sequence of four values in that order or a dict with exactly those four keys; every value a finite real number
+    (no bool).  ValueError for anything else.  Touches no device."""
+    if value is None:
+        return None
+    if isinstance(value, dict):
+        if set(value.keys()) != set(_FREEU_KEYS):
+            raise ValueError("x_info['freeu'] as a dict needs exactly the keys b1, b2, s1, s2, got %r" % (sorted(map(str, value.keys())),))
+        vals = [value[k] for k in _FREEU_KEYS]
+    elif isinstance(value, (tuple, list)) or (isinstance(value, np.ndarray) and value.ndim == 1):
+        vals = list(value)
+        if len(vals) != 4:
+            raise ValueError("x_info['freeu'] must hold four values (b1, b2, s1, s2), got %d" % len(vals))
+    else:
+        raise ValueError("x_info['freeu'] must be None, a sequence (b1, b2, s1, s2) or a dict with those keys, got %r" % (value,))
+    out = []
+    for k, v in zip(_FREEU_KEYS, vals):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+            raise ValueError("x_info['freeu']: %s must be a finite real number, got %r" % (k, v))
+        out.append(float(v))
+    return None if all(v == 1.0 for v in out) else tuple(out)
+
+
+def _freeu_arg(x_info):
+    """x_info['freeu'] validated (freeu_setting) for the flow of x_info: None, or (b1, b2, s1, s2) on the 2-D image flow."""
+    setting = freeu_setting(x_info.get("freeu"))
+    if x_info.get("freeu") is not None and x_info.get("type") != "image":
+        raise ValueError("freeu applies to x_info['type'] == 'image' only (the 0-D text flow has no planes), got %r"
+                         % (x_info.get("type"),))
+    return setting
+
+
+def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -267,8 +336,17 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     batch shares (VD_v2_0.precompute_step_emb); emb_silu may then be None.
     deep: None, or (DeepCache, "store" | "reuse") with (a, b) = deep_cut(data_net, cache.depth).  "store": steps[0:b], a side
     copy of h into the cache, steps[b:] -- the eps of the plain forward, bit for bit.  "reuse": steps[0:a] for its skips (its h
-    is dropped), h = the kept feature, steps[b:]."""
+    is dropped), h = the kept feature, steps[b:].
+    freeu: None, or (b1, b2, s1, s2) of freeu_setting: every skip load of a stage whose (b, s) is not (1, 1) hands h and the popped
+    skip to ops.freeu and goes on with its two fresh tensors (freeu_stages gives the widths).  In a cached walk the kept feature
+    stays the tensor in front of the load; the stage is applied each time a walk consumes it."""
     cut = None
+    fmap = None
+    if freeu is not None:
+        if x.dim() != 4:
+            raise ValueError("freeu needs a 2-D data net (x_info['type'] == 'image')")
+        W1, W2 = freeu_stages(data_net)[:2]
+        fmap = {w: bs for w, bs in ((W1, (freeu[0], freeu[2])), (W2, (freeu[1], freeu[3]))) if bs != (1.0, 1.0)}
     if deep is not None:
         if x.dim() != 4:
             raise ValueError("deep_cache needs a 2-D data net (x_info['type'] == 'image')")
@@ -363,7 +441,8 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     arena.begin(x.device)
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
-                              h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)))
+                              h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
+                              fmap or None)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -403,8 +482,9 @@ def _fork_region(steps, hw0, thr):
     return (a, b) if depth == 0 and any(st[0] == "c" for st in steps[a:b]) else None
 
 
-def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None):
-    """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk."""
+def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None):
+    """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
+    the active FreeU stages."""
     state = {"shared": shared}
 
     def walk(lo, hi, h, hs, sl=None):
@@ -436,6 +516,11 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 hs.append(h)
             elif st[0] == "load":
                 skip = hs.pop()
+                bs = None if fmap is None else fmap.get(h.shape[-1])
+                if bs is not None:
+                    # two fresh tensors (the skip belongs to the stack, h may be the kept feature of a cached walk); a copy
+                    # carries no producer statistics, so the consuming GroupNorm and the folded 1x1 skip conv measure them
+                    h, skip = ops.freeu(h, skip, bs[0], bs[1])
         assert skip is None
         return h
 
@@ -654,10 +739,11 @@ class VD_v2_0(nn.Module):
         glayer_ptr = x_type if self.global_layer_ptr is None else self.global_layer_ptr
         rows = x_info.get("emb_rows")   # extension key: the t-only part precomputed for a batch that shares its timestep
         deep = _deep_arg(x_info)        # extension key: (DeepCache, "store" | "reuse"), see run_unet
+        freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows, deep=deep).to(x.dtype)
+                        emb_rows=rows, deep=deep, freeu=freeu).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -666,9 +752,10 @@ class VD_v2_0(nn.Module):
         assert mixing_type in ("attention", "layer")
         rows = x_info.get("emb_rows")
         deep = _deep_arg(x_info)
+        freeu = _freeu_arg(x_info)
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
         specs = [(self.diffuser[ci["type"]].context_blocks, self._prep(ci["c"]), ci["ratio"], ci.get("kv_cache"))
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
-                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep).to(x.dtype)
+                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu).to(x.dtype)

@@ -1324,6 +1324,93 @@ def window_merge(eps_win, offs, wgt, inv_den, H, W, valid, wrap, first, last, ac
     return out if last else acc
 
 
+_freeu_tables = {}
+_freeu_lock = threading.Lock()
+
+
+def freeu_turn(k, n):
+    """(cos, sin) of k / n of a turn in float64, the angle reduced on integers first (k mod n); a multiple of a quarter turn
+    gives exactly 0 or +-1."""
+    import math
+    k, n = int(k) % int(n), int(n)
+    if (4 * k) % n == 0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[(4 * k) // n]
+    a = 2.0 * math.pi * k / n
+    return math.cos(a), math.sin(a)
+
+
+def freeu_tables_host(H, W):
+    """The six trig tables of FreeU's skip filter (contract in include/vd_hip.h) as float32 numpy arrays (cy, sy [H], cx, sx [W],
+    cxy, sxy [H W]): float64 values rounded once to fp32.  Needs no device."""
+    import numpy as np
+    H, W = int(H), int(W)
+    if H < 2 or W < 2:
+        raise ValueError("freeu: the plane is %d x %d, H and W must be at least 2" % (H, W))
+    ty = np.array([freeu_turn(p, H) for p in range(H)], dtype=np.float64)
+    tx = np.array([freeu_turn(q, W) for q in range(W)], dtype=np.float64)
+    txy = np.array([freeu_turn(p * W + q * H, H * W) for p in range(H) for q in range(W)], dtype=np.float64)
+    return tuple(np.ascontiguousarray(t[:, i]).astype(np.float32) for t in (ty, tx, txy) for i in (0, 1))
+
+
+def freeu_tables(H, W, device):
+    """freeu_tables_host(H, W) as fp32 tensors on `device` (views of one buffer), built once per (H, W, device).  A first use
+    copies from the host, so it must lie outside graph capture (the samplers' eager first step makes it)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(H), int(W), str(device))
+    with _freeu_lock:
+        tabs = _freeu_tables.get(key)
+        if tabs is None:
+            host = freeu_tables_host(H, W)
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise VdHipError("freeu: the tables of a %d x %d plane must exist before a forward is captured into a graph" % (H, W))
+            import numpy as np
+            flat = torch.from_numpy(np.concatenate(host)).to(device)
+            if device.type == "cuda":
+                # once per (H, W, device): the tables are read from whichever stream meets them later (forked branches)
+                torch.cuda.current_stream(device).synchronize()
+            tabs, o = [], 0
+            for t in host:
+                tabs.append(flat[o:o + t.size])
+                o += t.size
+            tabs = _freeu_tables[key] = tuple(tabs)
+    return tabs
+
+
+def _freeu_scalar(v, name):
+    import math
+    import numbers
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(float(v)):
+        raise ValueError("freeu: %s must be a finite real number, got %r" % (name, v))
+    return float(v)
+
+
+def freeu(h, skip, b, s):
+    """One stage of FreeU at a skip concatenation (contract in include/vd_hip.h): h [B, H, W, C0] and skip [B, H, W, C1], both
+    channels-last fp16 (contiguous batch-slice views included) -> (h2, skip2), fresh tensors: the first C0 // 2 channels of h
+    scaled by b, the others copied; every plane of skip with its lowest frequencies scaled by s.  One launch.  ValueError unless
+    C0 and C1 are multiples of 8, H, W >= 2 and b, s finite real numbers."""
+    _req(h, "h"); _req(skip, "skip")
+    b, s = _freeu_scalar(b, "b"), _freeu_scalar(s, "s")
+    if h.dim() != 4 or skip.dim() != 4 or tuple(h.shape[:3]) != tuple(skip.shape[:3]):
+        raise ValueError("freeu: h %s and skip %s must be [B, H, W, C0] and [B, H, W, C1]" % (tuple(h.shape), tuple(skip.shape)))
+    B, H, W, C0 = h.shape
+    C1 = skip.shape[3]
+    if C0 % 8 or C1 % 8 or C0 < 8 or C1 < 8:
+        raise ValueError("freeu: C0 = %d and C1 = %d must be multiples of 8" % (C0, C1))
+    if H < 2 or W < 2:
+        raise ValueError("freeu: the plane is %d x %d, H and W must be at least 2" % (H, W))
+    if B < 1:
+        raise ValueError("freeu: empty batch")
+    tabs = freeu_tables(H, W, h.device)
+    h2, skip2 = torch.empty_like(h), torch.empty_like(skip)
+    with _Timed("freeu_kernel", 8.0 * skip.numel(), 4.0 * skip.numel() + 4.0 * h.numel()):
+        _check(lib().vd_freeu_f16(_ptr(h), _ptr(skip), _ptr(h2), _ptr(skip2), *[_ptr(t) for t in tabs], B, H, W, C0, C1, b, s,
+                                  _stream()))
+    return h2, skip2
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1555,7 +1642,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "freeu", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
