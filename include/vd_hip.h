@@ -603,6 +603,29 @@ int vd_window_merge_f16(const void* eps_win, float* acc, void* eps, const float*
                         const int32_t* offs, int RB, int C, int H, int W, int h, int w, int slots, int valid, int wrap,
                         int first, int last, hipStream_t stream);
 
+/* Regional prompts on the windowed path (the region-based generation of MultiDiffusion, section 4.3): every region r has a mask
+ * on the canvas latent grid and contexts of its own, every (region, chunk of windows) is one UNet forward, and the predictions
+ * are fused weighted per pixel by window weight x region mask.  vd_window_merge_masked_f16 is one launch of that fusion: the
+ * arguments, layouts and thread ownership of vd_window_merge_f16 plus mask, fp32 [H, W] in device memory, the region of this
+ * launch (shared by all RB rows):
+ *   a  = first ? 0 : acc[...]
+ *   mv = mask[Y, X]
+ *   if mv != 0:                                 a zero mask adds nothing: a NaN predicted outside a region never reaches a
+ *     for k = 0 .. valid-1 ascending, if window k covers the pixel at (i, j):
+ *         wm = wgt[i, j] * mv                   one fp32 multiply, rounded once
+ *         a  = fmaf(wm, (float)eps_win[rb, k, c, i, j], a)
+ *   acc[...] = a  unless first && last
+ *   if last: eps[...] = fp16(a * inv_den[Y, X])     one fp32 multiply, then one rounding to fp16
+ * first / last span all (region, chunk) launches of a step: the sum runs region-major, inside a region in ascending window
+ * order, and acc is exact fp32 between launches, so the split into launches does not decide a bit.  inv_den is the reciprocal
+ * of the sum over regions and covering windows of the fp32 products wm (windows.region_inv_den); with one region whose mask is
+ * all ones the launch gives vd_window_merge_f16's bits.  Mask values are expected finite in [0, 1] (windows.region_masks_arg)
+ * and are not validated here.  Neither allocates nor synchronises (capturable).  Returns < 0 (vd_last_error) for what
+ * vd_window_merge_f16 refuses and for a null mask. */
+int vd_window_merge_masked_f16(const void* eps_win, float* acc, void* eps, const float* wgt, const float* mask,
+                               const float* inv_den, const int32_t* offs, int RB, int C, int H, int W, int h, int w, int slots,
+                               int valid, int wrap, int first, int last, hipStream_t stream);
+
 /* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024; not in the reference) at one skip concatenation of the
  * UNet's decoder.  The setting is four real numbers (b1, b2, s1, s2).  With W1 the width of the widest h that enters any
  * output-stage block of the 2-D data net and W2 = W1 / 2 (integer), a skip load whose entering h [B, H, W, C0] has C0 == W1 is

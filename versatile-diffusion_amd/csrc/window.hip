@@ -1,6 +1,6 @@
-// Windowed (MultiDiffusion) sampling, the two kernels around the UNet forward of a step (gfx950): window_gather cuts the canvas
+// Windowed (MultiDiffusion) sampling, the kernels around the UNet forward of a step (gfx950): window_gather cuts the canvas
 // latent into the batch of windows the UNet sees, window_merge fuses the windows' predictions back into one canvas-shaped
-// prediction.  Contract (layouts, the order of the sum, the roundings): include/vd_hip.h; the tables: lib/model_zoo/windows.py.
+// prediction, window_merge_masked does the same for one region of a regional-prompt call (a mask per launch).  Contract (layouts, the order of the sum, the roundings): include/vd_hip.h; the tables: lib/model_zoo/windows.py.
 // The canvas is small (4 x 64 x 256 elements per sample), so both kernels are the plain form: one work item per output piece,
 // consecutive lanes on consecutive addresses, no shared memory, no atomics.
 #include "vd_common.h"
@@ -90,6 +90,40 @@ __global__ void window_merge_kernel(const f16* eps_win, float* acc, f16* eps, co
     }
 }
 
+// window_merge_kernel for one region of a regional-prompt call: the same thread layout, coverage test and order, with the
+// region's mask value of the pixel multiplied into the weight -- wm = wgt * mask as an fp32 product of its own, then the same
+// fmaf.  A pixel the region does not own (mask 0) skips the windows altogether, so whatever the UNet predicted there (a NaN
+// included) never meets the sum.  first / last span all (region, chunk) launches of a step.
+__global__ void window_merge_masked_kernel(const f16* eps_win, float* acc, f16* eps, const float* wgt, const float* mask,
+                                           const float* inv_den, const int32_t* offs, int C, int H, int W, int h, int w,
+                                           int slots, int valid, int wrap, int first, int last, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t hw = (size_t)h * w;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
+        size_t r = t;
+        const int X = (int)(r % W); r /= W;
+        const int Y = (int)(r % H); r /= H;
+        const int c = (int)(r % C);
+        const size_t rb = r / C;
+        float a = first ? 0.f : acc[t];
+        const float mv = mask[(size_t)Y * W + X];
+        if (mv != 0.f) {
+            for (int k = 0; k < valid; ++k) {
+                const int i = Y - offs[2 * k];
+                if (i < 0 || i >= h) continue;
+                int j = X - offs[2 * k + 1];
+                if (wrap) j = window_mod(j, W);
+                if (j < 0 || j >= w) continue;
+                const size_t p = (size_t)i * w + j;
+                const float wm = wgt[p] * mv;
+                a = fmaf(wm, (float)eps_win[((rb * slots + k) * C + c) * hw + p], a);
+            }
+        }
+        if (!(first && last)) acc[t] = a;
+        if (last) eps[t] = window_round_f16(a * inv_den[(size_t)Y * W + X]);
+    }
+}
+
 }  // namespace
 
 extern "C" int vd_window_gather_f16(const void* x, void* win, const int32_t* offs, int B, int C, int H, int W, int h, int w,
@@ -118,4 +152,22 @@ extern "C" int vd_window_merge_f16(const void* eps_win, float* acc, void* eps, c
     hipLaunchKernelGGL(window_merge_kernel, dim3(grid_for(n)), dim3(256), 0, stream, (const f16*)eps_win, acc, (f16*)eps, wgt,
                        inv_den, offs, C, H, W, h, w, slots, valid, wrap != 0, first, last, n);
     return vd_check_launch("vd_window_merge_f16");
+}
+
+extern "C" int vd_window_merge_masked_f16(const void* eps_win, float* acc, void* eps, const float* wgt, const float* mask,
+                                          const float* inv_den, const int32_t* offs, int RB, int C, int H, int W, int h, int w,
+                                          int slots, int valid, int wrap, int first, int last, hipStream_t stream) {
+    first = first != 0;
+    last = last != 0;
+    VD_REQUIRE(eps_win && wgt && mask && inv_den && offs, "vd_window_merge_masked_f16: null pointer");
+    VD_REQUIRE(acc || (first && last), "vd_window_merge_masked_f16: acc may be NULL only when first && last");
+    VD_REQUIRE(eps || !last, "vd_window_merge_masked_f16: the last launch needs eps");
+    VD_REQUIRE(RB > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0 && slots > 0,
+               "vd_window_merge_masked_f16: sizes must be positive");
+    VD_REQUIRE(h <= H && w <= W, "vd_window_merge_masked_f16: window %d x %d does not fit the canvas %d x %d", h, w, H, W);
+    VD_REQUIRE(valid >= 1 && valid <= slots, "vd_window_merge_masked_f16: valid = %d outside [1, %d]", valid, slots);
+    const size_t n = (size_t)RB * C * H * W;
+    hipLaunchKernelGGL(window_merge_masked_kernel, dim3(grid_for(n)), dim3(256), 0, stream, (const f16*)eps_win, acc, (f16*)eps,
+                       wgt, mask, inv_den, offs, C, H, W, h, w, slots, valid, wrap != 0, first, last, n);
+    return vd_check_launch("vd_window_merge_masked_f16");
 }

@@ -33,6 +33,21 @@ def latent_mask(mask, mode="max", factor=8):
     return pool(mask.float(), factor)
 
 
+def region_masks(pixel_masks, mode="area", factor=8, background=True):
+    """Pixel masks of the regions of a regional-prompt call [R, 1, Hp, Wp] (1 = the region owns the pixel; float or bool) ->
+    (fp32 [R or R + 1, Hp / factor, Wp / factor] for x_info["region_masks"], whether a region was appended).  Every mask is
+    pooled by latent_mask(mode, factor).  background=True appends clip(1 - sum_r m_r, 0, 1) as a last region when that is non-zero
+    anywhere: the call then needs one more conditioning, the prompt of whatever the masks leave open."""
+    if pixel_masks.dim() != 4 or pixel_masks.shape[0] < 1:
+        raise ValueError("region_masks: expected [R, 1, H, W] pixel masks with R >= 1, got %s" % (tuple(pixel_masks.shape),))
+    m = latent_mask(pixel_masks, mode=mode, factor=factor)[:, 0]
+    if background:
+        rest = (1.0 - m.sum(0)).clamp(0.0, 1.0)
+        if bool((rest != 0).any()):
+            return torch.cat([m, rest[None]]), True
+    return m, False
+
+
 class adjust_rank(object):
     """Focus control of the image context: rescale the leading singular components of the (row-centred) CLIP token matrix
     -- lvl < 0.5 suppresses the top `max_drop_rank[0] + 1` ("semantic") components, lvl > 0.5 suppresses components

@@ -83,8 +83,16 @@ def _window_args(x_info, shape, model):
     when the plan has a single window (window == canvas): that call is the plain call and gives its bits.  The plan: the
     geometry "key" (h, w, sy, sx, wrap, weight, nc, m), "n" windows run as "nc" forwards of "m" slots per sample, "offsets"
     int32 [nc, m, 2] (the unused slots of the last forward repeat the last window), "wgt" fp32 [h, w] and "inv_den" fp32
-    [H, W].  Touches no device."""
-    window = x_info.get("window")
+    [H, W].
+    `region_masks` (regional prompts; real or bool [R, H, W] or [R, 1, H, W] on the canvas latent grid, values in [0, 1], shared
+    by the samples; windows.region_masks_arg) needs `window` and the image flow.  The plan is then built also for a single window
+    and holds "regions" R, "masks" fp32 [R, H, W] and as "inv_den" windows.region_inv_den; its key carries R as a ninth entry.
+    Touches no device (but reads masks given as a device tensor)."""
+    window, masks = x_info.get("window"), x_info.get("region_masks")
+    if masks is not None and x_info.get("type") != "image":
+        raise ValueError("region_masks applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if masks is not None and window is None:
+        raise ValueError("region_masks needs x_info['window'] (pass the canvas size for a plain image)")
     if window is None:
         return None
     if x_info.get("type") != "image":
@@ -103,11 +111,48 @@ def _window_args(x_info, shape, model):
     wgt = windows.window_weights(h, w, weight)
     n = offsets.shape[0]
     nc, m = windows.window_chunks(n, x_info.get("window_batch", 8))
-    if n == 1:
+    if masks is not None:
+        if torch.is_tensor(masks):
+            masks = masks.detach().cpu()
+            masks = (masks if masks.dtype == torch.bool else masks.float()).numpy()
+        masks = windows.region_masks_arg(masks, H, W)
+    elif n == 1:
         return None
     padded = np.concatenate([offsets, np.repeat(offsets[-1:], nc * m - n, axis=0)]).reshape(nc, m, 2)
-    return {"key": (h, w, sy, sx, bool(wrap), weight, nc, m), "n": n, "nc": nc, "m": m, "offsets": np.ascontiguousarray(padded),
-            "wgt": wgt, "inv_den": windows.window_inv_den(H, W, offsets, wgt, bool(wrap))}
+    plan = {"key": (h, w, sy, sx, bool(wrap), weight, nc, m), "n": n, "nc": nc, "m": m, "offsets": np.ascontiguousarray(padded),
+            "wgt": wgt}
+    if masks is None:
+        plan["inv_den"] = windows.window_inv_den(H, W, offsets, wgt, bool(wrap))
+    else:
+        plan.update(key=plan["key"] + (masks.shape[0],), regions=masks.shape[0], masks=masks,
+                    inv_den=windows.region_inv_den(H, W, offsets, wgt, masks, bool(wrap)))
+    return plan
+
+
+def _region_contexts(c_info_list, window, batch):
+    """The context list a regional-prompt call works on: region-major, R x len(c_info_list) shallow copies whose 'conditioning'
+    is region r's tensor -- entry r of a list or tuple of R tensors [B, L, D], or the context's plain tensor, shared by all
+    regions (each context decides for itself).  Without region masks (the plan has no "regions") the list comes back as it is,
+    and a conditioning list raises.  ValueError for a list of another length than R, entries whose shapes differ and a batch
+    other than `batch`.  Touches no device."""
+    R = None if window is None else window.get("regions")
+    for ci in c_info_list:
+        cond = ci.get("conditioning")
+        if not isinstance(cond, (list, tuple)):
+            continue
+        if R is None:
+            raise ValueError("a list of conditionings (one per region) needs x_info['region_masks']")
+        if len(cond) != R:
+            raise ValueError("the conditioning list has %d entries for %d region_masks" % (len(cond), R))
+        shapes = [tuple(c.shape) for c in cond]
+        if any(sh != shapes[0] for sh in shapes):
+            raise ValueError("the regions' conditionings differ in shape: %r" % (shapes,))
+        if len(shapes[0]) != 3 or shapes[0][0] != int(batch):
+            raise ValueError("a region's conditioning has shape %s, expected [%d, L, D]" % (shapes[0], int(batch)))
+    if R is None:
+        return c_info_list
+    return [dict(ci, conditioning=ci["conditioning"][r] if isinstance(ci["conditioning"], (list, tuple)) else ci["conditioning"])
+            for r in range(R) for ci in c_info_list]
 
 
 def cfg_guided_eps(eps, scale):
@@ -265,6 +310,8 @@ class DDIMSampler(object):
         window = _window_args(x_info, shape, self.model)
         if window is not None and interval > 1:
             raise ValueError("cache_interval > 1 does not combine with window: DeepCache would keep one feature per chunk of windows")
+        # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
+        c_info_list = _region_contexts(c_info_list, window, shape[0])
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
         # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
@@ -363,26 +410,45 @@ class DDIMSampler(object):
     def _window_state(plan, x, guided):
         """The device side of a windowed call's plan (_window_args) for the canvas latent x [B, C, H, W]: the tables "offs"
         (int32 [nc, m, 2]), "wgt", "inv_den", and the buffers "win" (fp16 [B, m, C, h, w], the UNet's input), "acc" (fp32
-        canvas, only with several forwards per step) and "eps" (fp16 [R B, C, H, W], what _eps returns).  Lives in the static
+        canvas, only with several forwards per step) and "eps" (fp16 [R B, C, H, W], what _eps returns).  With regions also
+        "rmask" (fp32 [R, H, W]); "rmask" and "inv_den" are then buffers that _load_state refills per call.  Lives in the static
         state entry, or for one call of the eager loop."""
         h, w = plan["key"][:2]
         B, C, H, W = x.shape
         rb = (2 if guided else 1) * B
         dev = dict(device=x.device)
-        return {"plan": plan, "offs": torch.from_numpy(plan["offsets"]).to(**dev), "wgt": torch.from_numpy(plan["wgt"]).to(**dev),
-                "inv_den": torch.from_numpy(plan["inv_den"]).to(**dev),
-                "win": torch.empty((B, plan["m"], C, h, w), dtype=torch.float16, **dev),
-                "acc": torch.empty((rb, C, H, W), dtype=torch.float32, **dev) if plan["nc"] > 1 else None,
-                "eps": torch.empty((rb, C, H, W), dtype=torch.float16, **dev)}
+        ws = {"plan": plan, "offs": torch.from_numpy(plan["offsets"]).to(**dev), "wgt": torch.from_numpy(plan["wgt"]).to(**dev),
+              "inv_den": torch.from_numpy(plan["inv_den"]).to(**dev),
+              "win": torch.empty((B, plan["m"], C, h, w), dtype=torch.float16, **dev),
+              "acc": torch.empty((rb, C, H, W), dtype=torch.float32, **dev) if plan["nc"] * plan.get("regions", 1) > 1 else None,
+              "eps": torch.empty((rb, C, H, W), dtype=torch.float16, **dev)}
+        if "regions" in plan:
+            ws["rmask"] = torch.from_numpy(plan["masks"]).to(**dev)
+        return ws
 
     def _eps_windowed(self, x_info, x, t, c_info_list, guided, single, emb_rows, ws):
         """The canvas prediction [R B, C, H, W] of a windowed step: per chunk of the plan, in order, ops.window_gather of the
         latent's windows, the UNet on them as a batch of B m samples (t and the contexts carry R B m rows, order (r, b, k)),
-        and ops.window_merge of what it predicts -- a sum in ascending window order, so the chunking does not decide a bit."""
+        and ops.window_merge of what it predicts -- a sum in ascending window order, so the chunking does not decide a bit.
+        With regions (regional prompts) c_info_list is the region-major list of _region_contexts: the chunks run once per region
+        with that region's slice of the contexts, and ops.window_merge_masked fuses them with the region's mask, region-major."""
         plan = ws["plan"]
         (h, w, _, _, wrap), nc, m = plan["key"][:5], plan["nc"], plan["m"]
         x = x.to(torch.float16).contiguous()
         B, C, H, W = x.shape
+        R = plan.get("regions")
+        if R is not None:
+            per = len(c_info_list) // R
+            assert per * R == len(c_info_list), "the context list is not region-major"
+            for r in range(R):
+                for k in range(nc):
+                    ops.window_gather(x, ws["offs"][k], h, w, wrap, out=ws["win"])
+                    e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list[r * per:(r + 1) * per], guided, single,
+                                  emb_rows)
+                    ops.window_merge_masked(e.to(torch.float16).contiguous().view(-1, m, C, h, w), ws["offs"][k], ws["wgt"],
+                                            ws["rmask"][r], ws["inv_den"], H, W, min(m, plan["n"] - k * m), wrap,
+                                            r == 0 and k == 0, r == R - 1 and k == nc - 1, acc=ws["acc"], out=ws["eps"])
+            return ws["eps"]
         for k in range(nc):
             ops.window_gather(x, ws["offs"][k], h, w, wrap, out=ws["win"])
             e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list, guided, single, emb_rows)
@@ -463,7 +529,8 @@ class DDIMSampler(object):
         # and DeepCache sampling with its depth (0: off), not its interval: one pair of graphs serves every interval >= 2, and
         # an uncached call never replays a graph that stores;
         # and windowed sampling with its whole geometry (h, w, sy, sx, wrap, weight, nc, m), None when off: the graph holds the
-        # gather / forward / merge chain of that plan and reads its tables;
+        # gather / forward / merge chain of that plan and reads its tables; with regional prompts the number of regions follows
+        # (the chain runs once per region), the masks do not: they are loaded per call;
         # and FreeU with its four values (b1, b2, s1, s2), None when off or all ones: the scalars are arguments of the captured
         # ops.freeu launches, and which stages launch at all depends on them -- one graph per setting)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
@@ -488,10 +555,14 @@ class DDIMSampler(object):
         self._static[key] = st                                 # most recently used last
         return st
 
-    def _load_state(self, st, x, c_info_list, inpaint, phi=0.):
-        """Copy this call's latent, contexts and inpainting tensors into the state and hand its context buffers and K/V caches to
-        c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None):
+        """Copy this call's latent, contexts, inpainting tensors and region masks (with their inv_den; `window` is the call's
+        plan) into the state and hand its context buffers and K/V caches to c_info_list.  Returns whether step 0 may be replayed
+        (else it runs eagerly and refreshes the K/V on its way)."""
         st["xs"].copy_(x)
+        if window is not None and "regions" in window:      # one kept graph serves every mask of the same R and geometry
+            st["window"]["rmask"].copy_(torch.from_numpy(window["masks"]))
+            st["window"]["inv_den"].copy_(torch.from_numpy(window["inv_den"]))
         if "phi" in st:
             st["phi"].fill_(phi)
         if inpaint is not None:
@@ -548,7 +619,7 @@ class DDIMSampler(object):
         cache_depth = depth if interval > 1 else 0
         st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window)
               or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window))
-        replay_first = self._load_state(st, x, c_info_list, inpaint, rescale)
+        replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
         steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
@@ -709,8 +780,8 @@ class DDIMSampler(object):
             raise ValueError("inpaint_mask: masked sampling runs whole sample() loops; p_sample_ddim* does not blend")
         if _cache_args(x_info, self.model)[0] > 1:
             raise ValueError("cache_interval > 1: DeepCache sampling runs whole sample() loops; p_sample_ddim* keeps no feature")
-        if x_info.get("window") is not None:
-            raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows")
+        if x_info.get("window") is not None or x_info.get("region_masks") is not None:
+            raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows (or regions)")
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list)

@@ -46,9 +46,12 @@ def sample_seeds(seed, lo, hi):
 
 
 def _slice_ctx(c_info, lo, hi):
+    """The context of samples [lo, hi).  A list or tuple conditioning holds one tensor per region (regional prompts): every
+    entry is sliced along its batch -- slicing the list itself would cut regions, not samples."""
     out = dict(c_info)
     for k in ("conditioning", "unconditional_conditioning"):
-        out[k] = c_info[k][lo:hi]
+        v = c_info[k]
+        out[k] = type(v)(c[lo:hi] for c in v) if isinstance(v, (list, tuple)) else v[lo:hi]
     return out
 
 
@@ -93,7 +96,7 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
                       images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
-                      window_weight="uniform", window_batch=8, freeu=None):
+                      window_weight="uniform", window_batch=8, freeu=None, region_masks=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -116,7 +119,11 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
     windows lie on the latent's H and W, so a rank's slice of the batch sees the same plan as the whole batch.
 
     freeu: the samplers' x_info['freeu'] (FreeU, vd.freeu_setting: (b1, b2, s1, s2) or a dict of them; None = off, and then the
-    key is not set).  A sample's filtered skips do not depend on the batch it runs in, so neither on the rank."""
+    key is not set).  A sample's filtered skips do not depend on the batch it runs in, so neither on the rank.
+
+    region_masks: the samplers' x_info['region_masks'] (regional prompts on the windowed path, ddim._window_args; None = off, and
+    then the key is not set; it needs `window`).  A context's 'conditioning' may then be a list of one [B, L, D] tensor per
+    region, sliced per sample (_slice_ctx).  The masks are shared by the samples, so every rank sees the same ones."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
 
@@ -149,6 +156,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
         if window is not None:
             x_info.update(window=window, window_stride=window_stride, window_wrap=window_wrap, window_weight=window_weight,
                           window_batch=window_batch)
+        if region_masks is not None:
+            x_info["region_masks"] = region_masks
         if freeu is not None:
             x_info["freeu"] = freeu
         from .dpm_solver import DPMSolverSDESampler

@@ -1,7 +1,9 @@
 """Host tables of windowed (MultiDiffusion, Bar-Tal et al. 2023) sampling: where the windows lie on the canvas latent, the
 weight a window gives each of its pixels, the reciprocal of the weights that land on a canvas pixel, and how the windows of a
-step are split into UNet forwards of one shape.  Pure numpy; touches no device.  The kernels that read these tables:
-ops.window_gather / ops.window_merge (contract in include/vd_hip.h); the samplers' use of them: ddim._window_args."""
+step are split into UNet forwards of one shape; and for regional prompts (MultiDiffusion section 4.3: one context per masked
+region) the region masks and the reciprocal of weight x mask summed over regions and windows.  Pure numpy; touches no device.
+The kernels that read these tables: ops.window_gather / ops.window_merge / ops.window_merge_masked (contract in
+include/vd_hip.h); the samplers' use of them: ddim._window_args."""
 import numpy as np
 
 
@@ -92,3 +94,42 @@ def window_chunks(Wn, window_batch):
         raise ValueError("window_batch must be an int >= 1 (and Wn >= 1), got %r" % ((Wn, window_batch),))
     nc = -(-Wn // window_batch)
     return nc, -(-Wn // nc)
+
+
+def region_masks_arg(masks, H, W):
+    """fp32 [R, H, W]: the region masks of a regional-prompt call (x_info['region_masks']) on the H x W canvas latent grid, from
+    a real or bool array [R, H, W] or [R, 1, H, W].  ValueError for another rank or shape, R < 1, and values that are not
+    finite or lie outside [0, 1]."""
+    m = np.asarray(masks)
+    if m.dtype == np.bool_:
+        m = m.astype(np.float32)
+    if m.dtype.kind not in "fiu":
+        raise ValueError("region_masks must be real or bool, got dtype %s" % (m.dtype,))
+    if m.ndim == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.ndim != 3 or tuple(m.shape[1:]) != (H, W):
+        raise ValueError("region_masks has shape %s, expected [R, %d, %d] or [R, 1, %d, %d]" % (np.shape(masks), H, W, H, W))
+    if m.shape[0] < 1:
+        raise ValueError("region_masks needs at least one region, got shape %s" % (np.shape(masks),))
+    m = np.ascontiguousarray(m, dtype=np.float32)
+    if not np.all(np.isfinite(m)) or m.min() < 0 or m.max() > 1:
+        raise ValueError("region_masks must hold finite values in [0, 1]")
+    return m
+
+
+def region_inv_den(H, W, offsets, weights, masks, wrap):
+    """fp32 [H, W]: 1 / (the sum over the regions r and the windows k that cover the pixel of wm = fp32(wgt_k x mask_r), the
+    products the merge kernel forms) -- float64 sum, float64 reciprocal, one rounding.  With one region whose mask is all ones
+    this is window_inv_den, bit for bit.  ValueError for pixels no region owns (or no window covers)."""
+    weights = np.asarray(weights, dtype=np.float32)
+    masks = np.asarray(masks, dtype=np.float32)
+    h, w = weights.shape
+    den = np.zeros((H, W), dtype=np.float64)
+    cols = np.arange(w)
+    for mask in masks:
+        for oy, ox in np.asarray(offsets).reshape(-1, 2):
+            ys, xs = slice(int(oy), int(oy) + h), (int(ox) + cols) % W if wrap else int(ox) + cols
+            den[ys, xs] += (weights * mask[ys, xs]).astype(np.float64)        # the fp32 product, rounded, then widened
+    if not np.all(den > 0):
+        raise ValueError("region_masks leave %d canvas pixels uncovered; add a background region" % int(np.sum(~(den > 0))))
+    return (1.0 / den).astype(np.float32)

@@ -121,6 +121,7 @@ PROTOTYPES = {
     "vd_masked_blend_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, _P]),
     "vd_window_gather_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vd_window_merge_f16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vd_window_merge_masked_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vd_freeu_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "vd_q_sample_f16": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),
     "vd_nchw_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -1287,17 +1287,13 @@ def window_gather(x, offs, h, w, wrap, out=None):
     return out
 
 
-def window_merge(eps_win, offs, wgt, inv_den, H, W, valid, wrap, first, last, acc=None, out=None):
-    """One launch of the windows' fusion (contract in include/vd_hip.h): eps_win fp16 [RB, slots, C, h, w] (a chunk of the
-    UNet's window predictions), offs device int32 [slots, 2], wgt fp32 [h, w], inv_den fp32 [H, W]; the first `valid` slots are
-    summed in ascending order onto acc (fp32 [RB, C, H, W]; started at 0 when `first`), and when `last` out (fp16
-    [RB, C, H, W]) = fp16(acc * inv_den).  acc is needed unless first and last.  Returns out when `last`, else acc."""
+def _window_merge_args(eps_win, offs, wgt, inv_den, H, W, valid, first, last, acc, out):
+    """The checks window_merge and window_merge_masked share; (RB, C, h, w, slots, acc, out) with the buffers made when absent."""
     _req(eps_win, "eps_win"); _req(wgt, "wgt", torch.float32); _req(inv_den, "inv_den", torch.float32)
     slots = _window_table(offs)
     if eps_win.dim() != 5 or eps_win.shape[1] != slots:
         raise VdHipError("eps_win has shape %s, expected [RB, %d, C, h, w]" % (tuple(eps_win.shape), slots))
     RB, _, C, h, w = eps_win.shape
-    H, W, valid, first, last = int(H), int(W), int(valid), bool(first), bool(last)
     if not (1 <= h <= H and 1 <= w <= W):
         raise VdHipError("a window of %d x %d does not fit the canvas %d x %d" % (h, w, H, W))
     if tuple(wgt.shape) != (h, w):
@@ -1319,8 +1315,36 @@ def window_merge(eps_win, offs, wgt, inv_den, H, W, valid, wrap, first, last, ac
     _req(out, "out")
     if out is not None and tuple(out.shape) != canvas:
         raise VdHipError("out has shape %s, expected %s" % (tuple(out.shape), canvas))
+    return RB, C, h, w, slots, acc, out
+
+
+def window_merge(eps_win, offs, wgt, inv_den, H, W, valid, wrap, first, last, acc=None, out=None):
+    """One launch of the windows' fusion (contract in include/vd_hip.h): eps_win fp16 [RB, slots, C, h, w] (a chunk of the
+    UNet's window predictions), offs device int32 [slots, 2], wgt fp32 [h, w], inv_den fp32 [H, W]; the first `valid` slots are
+    summed in ascending order onto acc (fp32 [RB, C, H, W]; started at 0 when `first`), and when `last` out (fp16
+    [RB, C, H, W]) = fp16(acc * inv_den).  acc is needed unless first and last.  Returns out when `last`, else acc."""
+    H, W, valid, first, last = int(H), int(W), int(valid), bool(first), bool(last)
+    RB, C, h, w, slots, acc, out = _window_merge_args(eps_win, offs, wgt, inv_den, H, W, valid, first, last, acc, out)
     _check(lib().vd_window_merge_f16(_ptr(eps_win), _ptr(acc), _ptr(out), _ptr(wgt), _ptr(inv_den), _ptr(offs), RB, C, H, W,
                                      h, w, slots, valid, int(bool(wrap)), int(first), int(last), _stream()))
+    return out if last else acc
+
+
+def window_merge_masked(eps_win, offs, wgt, mask, inv_den, H, W, valid, wrap, first, last, acc=None, out=None):
+    """One launch of the fusion of a regional-prompt step (vd_window_merge_masked_f16 in include/vd_hip.h): window_merge with
+    the weight of every term multiplied by mask fp32 [H, W], the region this chunk of predictions was made for; a pixel whose
+    mask is 0 takes nothing from them.  `first` / `last` span all (region, chunk) launches of the step and inv_den is
+    windows.region_inv_den.  Returns out when `last`, else acc."""
+    H, W, valid, first, last = int(H), int(W), int(valid), bool(first), bool(last)
+    _req(mask, "mask", torch.float32)
+    if mask is None or tuple(mask.shape) != (H, W):
+        raise VdHipError("mask has shape %s, expected %s" % (None if mask is None else tuple(mask.shape), (H, W)))
+    RB, C, h, w, slots, acc, out = _window_merge_args(eps_win, offs, wgt, inv_den, H, W, valid, first, last, acc, out)
+    if mask.device != eps_win.device:
+        raise VdHipError("mask lives on %s, eps_win on %s" % (mask.device, eps_win.device))
+    _check(lib().vd_window_merge_masked_f16(_ptr(eps_win), _ptr(acc), _ptr(out), _ptr(wgt), _ptr(mask), _ptr(inv_den),
+                                            _ptr(offs), RB, C, H, W, h, w, slots, valid, int(bool(wrap)), int(first), int(last),
+                                            _stream()))
     return out if last else acc
 
 
@@ -1642,7 +1666,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "freeu", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
