@@ -662,6 +662,42 @@ int vd_freeu_f16(const void* h, const void* skip, void* h_out, void* skip_out, c
                  const float* sx, const float* cxy, const float* sxy, int B, int H, int W, int C0, int C1, float b, float s,
                  hipStream_t stream);
 
+/* Perturbed-attention guidance (Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance", 2024;
+ * diffusers' pag_scale / pag_applied_layers; not in the reference).  A step predicts a further replica e_p in which chosen
+ * self-attention layers replace their attention map softmax(q k^T) by the identity, and combines
+ *     e = e_u + s (e_c - e_u) + s_pag (e_c - e_p)        (unguided, s == 1:  e = e_c + s_pag (e_c - e_p)).
+ * Two entry points (additive to ABI 8).
+ *
+ * vd_attention_ident_f16: the arguments of vd_attention_f16 plus ident_from.  Samples b < ident_from: exactly the call
+ * vd_attention_f16(q, k, v, out, ident_from, ...) -- the same kernel instances, so their bits are those of a call on these
+ * samples alone.  Samples b >= ident_from: out[b, n, c] = v[b, n, c] for every row n < Nq and column c < H * D, bit for bit
+ * (softmax replaced by I: every head keeps its own columns), through ldv / ldo and the sample strides sv / so; q and k of these
+ * samples are not read.  The copy is ONE launch of 16-byte accesses; ident_from == B launches no copy, ident_from == 0 no
+ * softmax kernel.  q / k / v may be column slices of one fused [B, N, 3 C] projection (ld = 3 C) and contiguous batch-slice
+ * views.  Returns < 0 (vd_last_error, the text starts with this entry's name) for null pointers, an empty problem, Nq != Nk,
+ * causal != 0, ident_from outside [0, B], H * D, a leading dimension or a sample stride of v / out that is no multiple of 8,
+ * ldv or ldo below H * D, v or out not 16-byte aligned, and whatever vd_attention_f16 refuses for the leading samples (its
+ * text follows the name).  Neither allocates nor synchronises (capturable). */
+int vd_attention_ident_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int Nq, int Nk, int D,
+                           int ldq, int ldk, int ldv, int ldo, int64_t sq, int64_t sk, int64_t sv, int64_t so,
+                           float scale, int causal, int ident_from, hipStream_t stream);
+
+/* vd_pag_fold_f16: eps is fp16 [reps][n], reps = 3 ([e_uncond ; e_cond ; e_perturbed]) or 2 ([e_cond ; e_perturbed]); w is a
+ * fp32[1] in DEVICE memory (one captured launch serves every weight).  With a = replica 0, c = replica reps - 2 (for reps == 2
+ * that is a itself) and p = replica reps - 1, replica 0 is rewritten in place, element by element:
+ *     d = fp32(c) - fp32(p)          one fp32 subtraction (the conversions are exact)
+ *     r = fmaf(w, d, fp32(a))        one fp32 fused multiply-add
+ *     a = fp16(r)                    a rounding of its own, to nearest even (never the exact fma result rounded to fp16)
+ * The other replicas are not written.  w == 0 writes nothing: replica 0 keeps its bits.
+ * reps == 3: the host loads w = -s_pag / (s - 1), formed in double and rounded once to fp32; then a' + s (c - a') is the
+ * formula above (up to that rounding), so every fused update vd_cfg_*_step_* and vd_cfg_rescale_factor_f16 run on the leading
+ * [2][n] unchanged -- the rescale targets the standard deviation of the unperturbed e_c, as diffusers'
+ * rescale_noise_cfg(noise_pred, noise_pred_text).  reps == 2: w = s_pag, and the unguided update reads the leading [n].
+ * Any n > 0: replicas that are all 16-byte aligned (eps aligned, n a multiple of 8) take 16-byte accesses, any other call one
+ * element per lane, with the same arithmetic.  An element's result depends on its three operands and w alone.  Returns < 0
+ * for a null pointer, n <= 0, reps outside {2, 3} or a misaligned eps / w.  Neither allocates nor synchronises (capturable). */
+int vd_pag_fold_f16(void* eps, int64_t n, int reps, const float* w, hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

@@ -21,7 +21,7 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import DeepCache, _freeu_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
+from .vd import DeepCache, _freeu_arg, _pag_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -199,6 +199,21 @@ def _rescale_arg(c_info_list):
     return phis[0]
 
 
+def replica_count(guided, pag):
+    """How many replicas of the latent batch the UNet sees in a step: 1 unguided, 2 under classifier-free guidance ([uncond ;
+    cond]) or unguided with perturbed-attention guidance ([cond ; perturbed]), 3 with both ([uncond ; cond ; perturbed])."""
+    return (2 if guided else 1) + (1 if pag else 0)
+
+
+def pag_weight(scale, pag_scale, guided):
+    """The fp32 weight ops.pag_fold reads (vd_pag_fold_f16, include/vd_hip.h), formed in float64 and rounded once.  Guided: the
+    fold rewrites e_u to a' = e_u + w (e_c - e_p) with w = -s_pag / (s - 1), so the update's a' + s (e_c - a') is
+    e_u + s (e_c - e_u) + s_pag (e_c - e_p).  Unguided: e_c + s_pag (e_c - e_p), w = s_pag."""
+    if guided:
+        return np.float32(-np.float64(pag_scale) / (np.float64(scale) - 1.0))
+    return np.float32(np.float64(pag_scale))
+
+
 _gc_lock = threading.Lock()
 _gc_holds = [0, False]      # captures in progress in this process; whether the collector was on when the first began
 
@@ -310,12 +325,14 @@ class DDIMSampler(object):
         window = _window_args(x_info, shape, self.model)
         if window is not None and interval > 1:
             raise ValueError("cache_interval > 1 does not combine with window: DeepCache would keep one feature per chunk of windows")
+        # x_info['pag_scale'] / ['pag_layers'] (extension keys, vd._pag_arg): None, or (s_pag, layers); raises like the others
+        pag = _pag_arg(x_info, self.model)
         # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
         c_info_list = _region_contexts(c_info_list, window, shape[0])
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
         # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
-        c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list, 1 if window is None else window["m"])
+        c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list, 1 if window is None else window["m"], pag is not None)
         dtype = c_info_list[0]["conditioning"].dtype
         x_info["x"], timesteps, blend_noise = self._start_latent(shape, x_info, masked, device, dtype)
         inpaint = None
@@ -333,11 +350,13 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint, phi, interval, depth, window)
+                                                 inpaint, phi, interval, depth, window, pag)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
             deep = DeepCache(depth) if interval > 1 else None
-            wstate = None if window is None else self._window_state(window, x, guided)      # once per call
+            wstate = None if window is None else self._window_state(window, x, guided, pag is not None)      # once per call
+            pag_step = None if pag is None else (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)),
+                                                                    device=x.device, dtype=torch.float32))
             if phi > 0.:
                 intermediates["guidance_rescale"] = []
             for ci in c_info_list:
@@ -348,7 +367,7 @@ class DDIMSampler(object):
                 x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                               noise_dropout=noise_dropout, rescale=rescale,
                                               deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"),
-                                              window=wstate)
+                                              window=wstate, pag=pag_step)
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
@@ -358,6 +377,8 @@ class DDIMSampler(object):
                         intermediates["guidance_rescale"].append(kfac)
         if interval > 1:
             intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
+        if pag is not None:
+            intermediates["pag_layers"] = pag[1]
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
 
@@ -382,13 +403,15 @@ class DDIMSampler(object):
             x = torch.randn(shape, device=device, dtype=dtype)
         return x, timesteps, x if noise is None else noise
 
-    def _cfg_contexts(self, c_info_list, slots=1):
+    def _cfg_contexts(self, c_info_list, slots=1, pag=False):
         """(copies, guided, scale, phi): shallow copies of the contexts with 'c', the batch the UNet sees ([uncond ; cond] under
         guidance), on the model's device.  The samplers work on the copies: 'c' (possibly a static buffer the captured graph
         reads) and 'kv_cache' never appear in the caller's dicts.  phi = c_info['guidance_rescale'] (extension key, default
         0 = off; cfg_rescale_factors): ValueError unless it is a real number in [0, 1] that all contexts agree on; an unguided
         call (scale == 1) ignores it, phi = 0.  slots > 1 (windowed sampling, the plan's m): the UNet's batch order is
-        (replica, sample, window slot), so every row is repeated `slots` times in place."""
+        (replica, sample, window slot), so every row is repeated `slots` times in place.
+        pag (perturbed-attention guidance): one more replica at the end, [uncond ; cond ; perturbed] or [cond ; perturbed]; the
+        perturbed replica carries the conditional context, which therefore appears twice."""
         scale = c_info_list[0]["unconditional_guidance_scale"]
         for ci in c_info_list:
             assert ci["unconditional_guidance_scale"] == scale, \
@@ -400,22 +423,25 @@ class DDIMSampler(object):
         copies = [dict(ci) for ci in c_info_list]
         for ci in copies:
             parts = [ci["unconditional_conditioning"], ci["conditioning"]] if guided else [ci["conditioning"]]
+            if pag:
+                parts.append(ci["conditioning"])
             if slots > 1:
                 parts = [p.repeat_interleave(slots, 0) for p in parts]
-            c = torch.cat(parts) if guided else parts[0]
+            c = torch.cat(parts) if len(parts) > 1 else parts[0]
             ci["c"] = c.to(self.model.device)
         return copies, guided, scale, phi
 
     @staticmethod
-    def _window_state(plan, x, guided):
+    def _window_state(plan, x, guided, pag=False):
         """The device side of a windowed call's plan (_window_args) for the canvas latent x [B, C, H, W]: the tables "offs"
         (int32 [nc, m, 2]), "wgt", "inv_den", and the buffers "win" (fp16 [B, m, C, h, w], the UNet's input), "acc" (fp32
-        canvas, only with several forwards per step) and "eps" (fp16 [R B, C, H, W], what _eps returns).  With regions also
+        canvas, only with several forwards per step) and "eps" (fp16 [R B, C, H, W], what _eps returns; R = replica_count(guided,
+        pag), so with perturbed-attention guidance the canvas prediction has a perturbed replica too).  With regions also
         "rmask" (fp32 [R, H, W]); "rmask" and "inv_den" are then buffers that _load_state refills per call.  Lives in the static
         state entry, or for one call of the eager loop."""
         h, w = plan["key"][:2]
         B, C, H, W = x.shape
-        rb = (2 if guided else 1) * B
+        rb = replica_count(guided, pag) * B
         dev = dict(device=x.device)
         ws = {"plan": plan, "offs": torch.from_numpy(plan["offsets"]).to(**dev), "wgt": torch.from_numpy(plan["wgt"]).to(**dev),
               "inv_den": torch.from_numpy(plan["inv_den"]).to(**dev),
@@ -426,7 +452,7 @@ class DDIMSampler(object):
             ws["rmask"] = torch.from_numpy(plan["masks"]).to(**dev)
         return ws
 
-    def _eps_windowed(self, x_info, x, t, c_info_list, guided, single, emb_rows, ws):
+    def _eps_windowed(self, x_info, x, t, c_info_list, guided, single, emb_rows, ws, pag=None):
         """The canvas prediction [R B, C, H, W] of a windowed step: per chunk of the plan, in order, ops.window_gather of the
         latent's windows, the UNet on them as a batch of B m samples (t and the contexts carry R B m rows, order (r, b, k)),
         and ops.window_merge of what it predicts -- a sum in ascending window order, so the chunking does not decide a bit.
@@ -444,28 +470,34 @@ class DDIMSampler(object):
                 for k in range(nc):
                     ops.window_gather(x, ws["offs"][k], h, w, wrap, out=ws["win"])
                     e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list[r * per:(r + 1) * per], guided, single,
-                                  emb_rows)
+                                  emb_rows, pag=pag)
                     ops.window_merge_masked(e.to(torch.float16).contiguous().view(-1, m, C, h, w), ws["offs"][k], ws["wgt"],
                                             ws["rmask"][r], ws["inv_den"], H, W, min(m, plan["n"] - k * m), wrap,
                                             r == 0 and k == 0, r == R - 1 and k == nc - 1, acc=ws["acc"], out=ws["eps"])
             return ws["eps"]
         for k in range(nc):
             ops.window_gather(x, ws["offs"][k], h, w, wrap, out=ws["win"])
-            e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list, guided, single, emb_rows)
+            e = self._eps(x_info, ws["win"].view(B * m, C, h, w), t, c_info_list, guided, single, emb_rows, pag=pag)
             ops.window_merge(e.to(torch.float16).contiguous().view(-1, m, C, h, w), ws["offs"][k], ws["wgt"], ws["inv_den"], H, W,
                              min(m, plan["n"] - k * m), wrap, k == 0, k == nc - 1, acc=ws["acc"], out=ws["eps"])
         return ws["eps"]
 
-    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None, window=None):
+    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None, window=None, pag=None):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
         so the data blocks in front of the first context block run once (extension key of this package's apply_model*).
         deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache').
         window: the _window_state of a windowed call -- x is the canvas, and so is what comes back (_eps_windowed).
-        x_info['freeu'] (FreeU, vd.freeu_setting) travels with every forward, so with windows it acts inside each window's."""
+        x_info['freeu'] (FreeU, vd.freeu_setting) travels with every forward, so with windows it acts inside each window's.
+        pag: None, or the layers of perturbed-attention guidance: one more replica, the last, runs those context blocks with
+        identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward."""
         if window is not None:
             assert deep is None, "DeepCache does not combine with windows"
-            return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window)
-        xi = {"type": x_info["type"], "x": x, "repeat": 2 if guided else 1}
+            return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window, pag)
+        reps = replica_count(guided, pag is not None)
+        xi = {"type": x_info["type"], "x": x, "repeat": reps}
+        if pag is not None:
+            assert deep is None, "DeepCache does not combine with pag"
+            xi["pag"] = (pag, (reps - 1) * x.shape[0])
         if emb_rows is not None:
             xi["emb_rows"] = emb_rows
         if deep is not None:
@@ -488,15 +520,17 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None, pag=False):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
         projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
         rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
         (fp32 [B], written by every step); and the graph.  cache_depth > 0 (DeepCache sampling): "graph" is the full step that
         stores the deep feature, "graph_shallow" the step that reuses it, and "deep" holds the one kept buffer both read.
         window (the plan of _window_args): "window" holds its tables and buffers (_window_state), and "ts" has a row per
-        window slot like the context batches."""
-        nb = (2 if guided else 1) * x.shape[0] * (1 if window is None else window["m"])
+        window slot like the context batches.  pag (perturbed-attention guidance on): "ts" and the window buffers have the rows
+        of replica_count(guided, pag) replicas, and "pag_w" is the fold's weight (fp32 [1], loaded per call: one graph serves
+        every positive pag_scale and every guidance scale)."""
+        nb = replica_count(guided, pag) * x.shape[0] * (1 if window is None else window["m"])
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
               "coef": torch.empty((self.coef_width,), device=x.device, dtype=torch.float32),
@@ -506,7 +540,9 @@ class DDIMSampler(object):
         if cache_depth > 0:
             st.update(graph_shallow=None, deep=DeepCache(cache_depth))
         if window is not None:
-            st["window"] = self._window_state(window, x, guided)
+            st["window"] = self._window_state(window, x, guided, pag)
+        if pag:
+            st["pag_w"] = torch.empty((1,), device=x.device, dtype=torch.float32)
         if rescale > 0.:
             st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
                       kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
@@ -532,15 +568,18 @@ class DDIMSampler(object):
         # gather / forward / merge chain of that plan and reads its tables; with regional prompts the number of regions follows
         # (the chain runs once per region), the masks do not: they are loaded per call;
         # and FreeU with its four values (b1, b2, s1, s2), None when off or all ones: the scalars are arguments of the captured
-        # ops.freeu launches, and which stages launch at all depends on them -- one graph per setting)
+        # ops.freeu launches, and which stages launch at all depends on them -- one graph per setting;
+        # and perturbed-attention guidance, (on?, layers): a graph captured with it runs one more replica, the identity attention of
+        # those context blocks and the fold; its scale is not in the key -- the fold's weight is loaded per call)
+        pag = _pag_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
                inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"],
-               _freeu_arg(x_info))
+               (pag is not None, None if pag is None else pag[1]), _freeu_arg(x_info))
         return key
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -551,20 +590,22 @@ class DDIMSampler(object):
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag)
         self._static[key] = st                                 # most recently used last
         return st
 
-    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None):
-        """Copy this call's latent, contexts, inpainting tensors and region masks (with their inv_den; `window` is the call's
-        plan) into the state and hand its context buffers and K/V caches to c_info_list.  Returns whether step 0 may be replayed
-        (else it runs eagerly and refreshes the K/V on its way)."""
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None):
+        """Copy this call's latent, contexts, inpainting tensors, region masks (with their inv_den; `window` is the call's
+        plan) and the weight of the perturbed-attention fold (pag_w, pag_weight) into the state and hand its context buffers and
+        K/V caches to c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
         st["xs"].copy_(x)
         if window is not None and "regions" in window:      # one kept graph serves every mask of the same R and geometry
             st["window"]["rmask"].copy_(torch.from_numpy(window["masks"]))
             st["window"]["inv_den"].copy_(torch.from_numpy(window["inv_den"]))
         if "phi" in st:
             st["phi"].fill_(phi)
+        if "pag_w" in st:
+            st["pag_w"].fill_(float(pag_w))
         if inpaint is not None:
             for k in ("x0", "noise", "mask"):
                 st[k].copy_(inpaint[k])
@@ -604,7 +645,7 @@ class DDIMSampler(object):
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
     def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
-                     phi=0., interval=1, depth=1, window=None):
+                     phi=0., interval=1, depth=1, window=None, pag=None):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry.  Returns (final fp16 latent, intermediates).
@@ -613,13 +654,18 @@ class DDIMSampler(object):
         update); each is captured the first time its kind of step is met behind step 0, which is full and, when eager, fills
         every cache either walk needs (the shallow walk runs a subset of the full walk's blocks at the same shapes).
         window (the plan of _window_args): the step's prediction is the fusion of the windows' (_eps_windowed); the update, the
-        rescale factors, the blend, the seeded noise and the solver histories see the canvas and nothing else."""
+        rescale factors, the blend, the seeded noise and the solver histories see the canvas and nothing else.
+        pag (None, or (s_pag, layers) of vd._pag_arg): the forward runs one more replica, perturbed, and ops.pag_fold folds its
+        prediction into replica 0 between the forward and the update; the update, the rescale factors, the blend, the noise and the
+        histories see the folded pair (or single) and nothing else, so every sampler on this loop gets it."""
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
-        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window))
-        replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window)
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pag is not None)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None))
+        replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window,
+                                        None if pag is None else pag_weight(scale, pag[0], guided))
+        reps = replica_count(guided, pag is not None)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
         steps_dev = torch.from_numpy(np.ascontiguousarray(np.flip(timesteps)).astype(np.int64)).to(x.device)
@@ -627,8 +673,11 @@ class DDIMSampler(object):
 
         def body(mode=None):
             eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows,
-                            None if mode is None else (st["deep"], mode), st.get("window"))
-            self._update_static(st, eps.contiguous(), guided)
+                            None if mode is None else (st["deep"], mode), st.get("window"), None if pag is None else pag[1])
+            eps = eps.contiguous()
+            if pag is not None:
+                eps = ops.pag_fold(eps, reps, st["pag_w"])      # the folded pair (single): what every update below reads
+            self._update_static(st, eps, guided)
 
         bodies = {"graph": body if interval == 1 else (lambda: body("store")), "graph_shallow": lambda: body("reuse")}
 
@@ -728,12 +777,14 @@ class DDIMSampler(object):
             return None
 
     def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None,
-              deep=None, window=None):
+              deep=None, window=None, pag=None):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
-        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep, window: _eps's."""
-        rows = (2 if guided else 1) * x.shape[0] * (1 if window is None else window["plan"]["m"])
+        the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep, window: _eps's.
+        pag: None, or (layers, the fold's weight as a device fp32 [1]) of perturbed-attention guidance."""
+        reps = replica_count(guided, pag is not None)
+        rows = reps * x.shape[0] * (1 if window is None else window["plan"]["m"])
         t_in = torch.full((rows,), step, device=x.device, dtype=torch.long)
-        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep, window=window)
+        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep, window=window, pag=None if pag is None else pag[0])
         sigma = float(self.ddim_sigmas[index])
         # drawn on every step like the reference's noise_like(x) (ddim.py:167 there): same generator consumption, and for
         # eta > 0 the same noise values as a reference running in fp16 on this device
@@ -750,6 +801,8 @@ class DDIMSampler(object):
                        a_prev=float(self.ddim_alphas_prev[index]), sigma=sigma,
                        sqrt_one_minus_at=float(self.ddim_sqrt_one_minus_alphas[index]), noise=noise)
         eps = eps.contiguous()
+        if pag is not None:
+            eps = ops.pag_fold(eps, reps, pag[1])
         if rescale is None:
             return ops.cfg_ddim_step(x, eps, **scalars) + (None,)
         kfac = ops.cfg_rescale_factor(eps, rescale[0], rescale[1], x.numel() // x.shape[0])
@@ -783,10 +836,13 @@ class DDIMSampler(object):
         if x_info.get("window") is not None or x_info.get("region_masks") is not None:
             raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows (or regions)")
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
+        pag = _pag_arg(x_info, self.model)      # so is perturbed-attention guidance: one more replica and the fold
         assert not use_original_steps and not repeat_noise
-        cis, guided, scale, phi = self._cfg_contexts(c_info_list)
+        cis, guided, scale, phi = self._cfg_contexts(c_info_list, pag=pag is not None)
         x = x_info["x"]
+        if pag is not None:
+            pag = (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)), device=x.device, dtype=torch.float32))
         xp, p0, _ = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
                                temperature, single, noise_dropout=noise_dropout,
-                               rescale=self._rescale_scalars(scale, phi, x.device))
+                               rescale=self._rescale_scalars(scale, phi, x.device), pag=pag)
         return xp.to(x.dtype), p0.to(x.dtype)

@@ -96,7 +96,8 @@ def sample_sharded(sample_fn, decode_fn, shape, c_info_list, seed, device, group
 def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_scale=7.5, eta=0., group=None,
                       images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
-                      window_weight="uniform", window_batch=8, freeu=None, region_masks=None):
+                      window_weight="uniform", window_batch=8, freeu=None, region_masks=None, pag_scale=None,
+                      pag_layers=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -120,6 +121,9 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     freeu: the samplers' x_info['freeu'] (FreeU, vd.freeu_setting: (b1, b2, s1, s2) or a dict of them; None = off, and then the
     key is not set).  A sample's filtered skips do not depend on the batch it runs in, so neither on the rank.
+
+    pag_scale, pag_layers: the samplers' x_info['pag_scale'] and x_info['pag_layers'] (perturbed-attention guidance, vd._pag_arg;
+    None = the key is not set).  The perturbed replica is per sample, so a rank's slice sees what the whole batch would.
 
     region_masks: the samplers' x_info['region_masks'] (regional prompts on the windowed path, ddim._window_args; None = off, and
     then the key is not set; it needs `window`).  A context's 'conditioning' may then be a list of one [B, L, D] tensor per
@@ -160,6 +164,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             x_info["region_masks"] = region_masks
         if freeu is not None:
             x_info["freeu"] = freeu
+        if pag_scale is not None:
+            x_info["pag_scale"] = pag_scale
+        if pag_layers is not None:
+            x_info["pag_layers"] = pag_layers
         from .dpm_solver import DPMSolverSDESampler
         if isinstance(sampler, DPMSolverSDESampler):
             world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -321,7 +321,86 @@ def _freeu_arg(x_info):
     return setting
 
 
-def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None):
+# ---- perturbed-attention guidance (x_info['pag_scale'], x_info['pag_layers']; forward key x_info['pag']) -------------------------
+# Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance" (2024); diffusers' pag_scale and
+# pag_applied_layers.  The samplers append one replica to the batch whose self-attention map is the identity in the chosen
+# context blocks (run_unet(pag=...)) and fold its prediction into the step's eps (ops.pag_fold, contract in include/vd_hip.h).
+def pag_context_blocks(net):
+    """(n, mid): the number of context blocks in the walk i_order + m_order + o_order of a 2-D data net and the walk index of the
+    middle stage's first one ("mid": 6 of the 16 at full width).  ValueError for a net without such a walk."""
+    from .openaimodel import UNetModel0D_Next
+    if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("i_order", "m_order", "o_order")):
+        raise ValueError("pag needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+    i_order, m_order, o_order = list(net.i_order), list(net.m_order), list(net.o_order)
+    n = sum(s == "c" for s in i_order + m_order + o_order)
+    if "c" not in m_order:
+        raise ValueError("pag: the middle stage of %s has no context block" % type(net).__name__)
+    return n, sum(s == "c" for s in i_order)
+
+
+def pag_layers(value, net):
+    """x_info['pag_layers'] as a sorted tuple of context-block indices in walk order: "mid" (also for None, the default) is the
+    middle stage's block; else an iterable of ints in [0, n).  ValueError (matching 'pag') for an empty list, duplicates, indices
+    out of range or anything that is no int.  Touches no device."""
+    n, mid = pag_context_blocks(net)
+    if value is None or (isinstance(value, str) and value == "mid"):
+        return (mid,)
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
+        raise ValueError("x_info['pag_layers'] must be 'mid' or an iterable of context-block indices, got %r" % (value,))
+    out = []
+    for v in value:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < n:
+            raise ValueError("x_info['pag_layers']: %r is no context-block index in [0, %d)" % (v, n))
+        out.append(int(v))
+    if not out:
+        raise ValueError("x_info['pag_layers'] is empty: pag needs at least one context block")
+    if len(set(out)) != len(out):
+        raise ValueError("x_info['pag_layers'] names a context block twice: %r" % (out,))
+    return tuple(sorted(out))
+
+
+def _pag_arg(x_info, model):
+    """The sampler keys of perturbed-attention guidance validated: None when x_info['pag_scale'] is absent, None or 0 (off: today's
+    call, 'pag_layers' is then ignored), else (s_pag as a float, the normalised layers of pag_layers) on the 2-D image flow.
+    ValueError (matching 'pag') for a scale that is no real number, negative or not finite, for another flow, and for the
+    combinations left out of scope on purpose: cache_interval > 1 (DeepCache would keep the deep feature of three replicas and
+    reuse a perturbed one) and region_masks (one perturbed replica per region).  Touches no device."""
+    value = x_info.get("pag_scale")
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(float(value)) or float(value) < 0.:
+        raise ValueError("x_info['pag_scale'] must be a finite real number >= 0, got %r" % (value,))
+    if float(value) == 0.:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("pag_scale applies to x_info['type'] == 'image' only (perturbed self-attention of the 2-D net), got %r"
+                         % (x_info.get("type"),))
+    cache = x_info.get("cache_interval", 1)
+    if not isinstance(cache, (bool, str)) and isinstance(cache, (int, np.integer)) and cache > 1:
+        raise ValueError("pag_scale with cache_interval > 1 is out of scope on purpose: DeepCache and pag do not combine")
+    if x_info.get("region_masks") is not None:
+        raise ValueError("pag_scale with region_masks is out of scope on purpose: regional prompts and pag do not combine")
+    return float(value), pag_layers(x_info.get("pag_layers"), model.diffuser[x_info["type"]])
+
+
+def _pag_fwd_arg(x_info, net):
+    """x_info['pag'] (extension key of apply_model*, set by the samplers) validated: None, or (layers, row0) -- the rows >= row0
+    of the batch, counted after replication, take identity self-attention in the context blocks `layers` (pag_layers) of `net`."""
+    pag = x_info.get("pag")
+    if pag is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("pag applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if not (isinstance(pag, (tuple, list)) and len(pag) == 2):
+        raise ValueError("x_info['pag'] must be (layers, row0), got %r" % (pag,))
+    row0 = pag[1]
+    if isinstance(row0, (bool, np.bool_)) or not isinstance(row0, (int, np.integer)) or row0 < 0:
+        raise ValueError("x_info['pag']: row0 must be an int >= 0, got %r" % (row0,))
+    return pag_layers(pag[0], net), int(row0)
+
+
+def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -339,7 +418,20 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     is dropped), h = the kept feature, steps[b:].
     freeu: None, or (b1, b2, s1, s2) of freeu_setting: every skip load of a stage whose (b, s) is not (1, 1) hands h and the popped
     skip to ops.freeu and goes on with its two fresh tensors (freeu_stages gives the widths).  In a cached walk the kept feature
-    stays the tensor in front of the load; the stage is applied each time a walk consumes it."""
+    stays the tensor in front of the load; the stage is applied each time a walk consumes it.
+    pag: None, or (layers, row0) of _pag_fwd_arg: in the context blocks whose walk index is in `layers` the rows >= row0 of the batch
+    (after replication; every context type's block at that index) run their self-attention with the identity map
+    (SpatialTransformer.forward(ident_from=...)); a half-batch branch holding samples [b0, b1) gets clamp(row0 - b0, 0, b1 - b0).
+    A forward with pag replicates h IN FRONT of the first context block (share = 1): the shared CFG head is not used, whichever
+    layers are named, so block 0 can be a perturbed layer and a perturbed replica never reads a shared self-attention.  It does
+    not combine with deep (ValueError)."""
+    if pag is not None:
+        if x.dim() != 4:
+            raise ValueError("pag needs a 2-D data net (x_info['type'] == 'image')")
+        if deep is not None:
+            raise ValueError("pag does not combine with deep_cache")
+        if not 0 <= pag[1] <= repeat * x.shape[0]:
+            raise ValueError("pag: row0 = %d is outside the batch of %d x %d rows" % (pag[1], repeat, x.shape[0]))
     cut = None
     fmap = None
     if freeu is not None:
@@ -363,6 +455,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
 
     # the walk, resolved to modules once: ("d", index, block) / ("c", modules, specs, ratios) / ("save",) / ("load",)
     steps = []
+    c_index = 0
     for ltype in list(data_net.i_order) + list(data_net.m_order) + list(data_net.o_order):
         if ltype == "d":
             di, blk = next(d_iter)
@@ -371,9 +464,10 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
             modules = [next(it) for it in c_iters]
             if mixing_type == "layer":
                 pick = int(npr.choice(len(modules), p=ratios))
-                steps.append(("c", [modules[pick]], [ctx_specs[pick]], [1.0]))
+                steps.append(("c", [modules[pick]], [ctx_specs[pick]], [1.0], c_index))
             else:
-                steps.append(("c", modules, list(ctx_specs), ratios))
+                steps.append(("c", modules, list(ctx_specs), ratios, c_index))
+            c_index += 1
         elif ltype == "save_hidden_feature":
             steps.append(("save",))
         elif ltype == "load_hidden_feature":
@@ -382,12 +476,14 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None, repeat=1):
+    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
-        repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them."""
+        repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them.
+        ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag)."""
         single = len(modules) == 1
+        pkw = {} if ident_from is None else {"ident_from": int(ident_from)}
         if repeat > 1:
-            assert single and sl is None
+            assert single and sl is None and ident_from is None
             return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat)
         kvs = [context_kv(m, sp) for m, sp in zip(modules, specs)]
         if sl is not None:
@@ -400,7 +496,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
         if single or not CTX_FORK or not h.is_cuda:
             out = None
             for module, spec, kv, r in zip(modules, specs, kvs, rs):
-                out = module(h, None, spec[1], kv=kv, alpha=1.0 if single else float(r), res=out)
+                out = module(h, None, spec[1], kv=kv, alpha=1.0 if single else float(r), res=out, **pkw)
             return out
         main = torch.cuda.current_stream()
         sides = _side_streams(h.device, len(modules) - 1)
@@ -413,7 +509,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
             with torch.cuda.stream(st):
                 tok = order.enter(st, first=i == 0)
                 out = module(h, None, spec[1], kv=kv, alpha=float(r), res=prev,
-                             sync=(None if prev_done is None else (lambda e=prev_done, s_=st: s_.wait_event(e))))
+                             sync=(None if prev_done is None else (lambda e=prev_done, s_=st: s_.wait_event(e))), **pkw)
                 ev = torch.cuda.Event()
                 ev.record(st)
                 order.leave(st, tok)
@@ -442,7 +538,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
                               h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
-                              fmap or None)
+                              fmap or None, pag)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -482,9 +578,10 @@ def _fork_region(steps, hw0, thr):
     return (a, b) if depth == 0 and any(st[0] == "c" for st in steps[a:b]) else None
 
 
-def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None):
+def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None,
+                   pag=None):
     """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
-    the active FreeU stages."""
+    the active FreeU stages.  pag: None, or (layers, row0) of run_unet."""
     state = {"shared": shared}
 
     def walk(lo, hi, h, hs, sl=None):
@@ -506,12 +603,16 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 if state["shared"]:  # the replicas diverge here
                     rep = lambda t: ops.repeat_batch(t, repeat)   # per-channel statistics of the tensors travel along
                     hs[:] = [rep(t) for t in hs]
-                    if CFG_HEAD_SHARE and len(st[1]) == 1 and sl is None and h.dim() == 4 and _shares_cfg_head(st[1][0]):
+                    if CFG_HEAD_SHARE and pag is None and len(st[1]) == 1 and sl is None and h.dim() == 4 and _shares_cfg_head(st[1][0]):
                         share = repeat   # ... inside the block, behind its self-attention: h goes in un-replicated
                     else:
                         h = rep(h)
                     state["shared"] = False
-                h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
+                if pag is not None and st[4] in pag[0]:
+                    b0, b1 = (0, h.shape[0]) if sl is None else sl
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, ident_from=min(max(pag[1] - b0, 0), b1 - b0))
+                else:
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
             elif st[0] == "save":
                 hs.append(h)
             elif st[0] == "load":
@@ -740,10 +841,11 @@ class VD_v2_0(nn.Module):
         rows = x_info.get("emb_rows")   # extension key: the t-only part precomputed for a batch that shares its timestep
         deep = _deep_arg(x_info)        # extension key: (DeepCache, "store" | "reuse"), see run_unet
         freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
+        pag = _pag_fwd_arg(x_info, self.diffuser[x_type])   # extension key: (layers, row0), see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows, deep=deep, freeu=freeu).to(x.dtype)
+                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -753,9 +855,10 @@ class VD_v2_0(nn.Module):
         rows = x_info.get("emb_rows")
         deep = _deep_arg(x_info)
         freeu = _freeu_arg(x_info)
+        pag = _pag_fwd_arg(x_info, self.diffuser[x_type])
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
         specs = [(self.diffuser[ci["type"]].context_blocks, self._prep(ci["c"]), ci["ratio"], ci.get("kv_cache"))
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
-                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu).to(x.dtype)
+                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag).to(x.dtype)

@@ -926,10 +926,13 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     return out
 
 
-def attention(q, k, v, heads, *, scale=None, causal=False, out=None):
+def attention(q, k, v, heads, *, scale=None, causal=False, out=None, ident_from=None):
     """q [B, Nq, *], k/v [B, Nk, *]: last-dim views (possibly column slices of a fused projection) with stride 1.
 
-    Head h uses columns h*D:(h+1)*D of each.  Returns [B, Nq, heads*D] contiguous."""
+    Head h uses columns h*D:(h+1)*D of each.  Returns [B, Nq, heads*D] contiguous.
+    ident_from (perturbed-attention guidance; None: the call above, unchanged): an int in [0, B]; the samples from it on take the
+    identity attention map, out[b] = v[b] bit for bit, the samples in front of it the softmax path with the bits of a call on
+    them alone (vd_attention_ident_f16: self-attention without a causal mask only)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda or t.dtype != torch.float16 or t.stride(-1) != 1 or t.dim() != 3:
             raise VdHipError("%s must be a 3-d fp16 GPU tensor with unit inner stride" % n)
@@ -940,6 +943,15 @@ def attention(q, k, v, heads, *, scale=None, causal=False, out=None):
         out = torch.empty((B, Nq, C), dtype=torch.float16, device=q.device)
     if scale is None:
         scale = D ** -0.5
+    if ident_from is not None:
+        if isinstance(ident_from, bool) or not isinstance(ident_from, int):
+            raise VdHipError("ident_from must be None or an int in [0, %d], got %r" % (B, ident_from))
+        soft = min(max(ident_from, 0), B)
+        with _Timed("attn_ident<%d>" % D, 4.0 * soft * Nq * Nk * C, 2.0 * soft * C * (2 * Nq + 2 * Nk) + 4.0 * (B - soft) * Nq * C):
+            _check(lib().vd_attention_ident_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, q.stride(1), k.stride(1),
+                                                v.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
+                                                float(scale), int(causal), ident_from, _stream()))
+        return out
     with _Timed(("attn_fwd_kernel<%d>" % D) + ((" Nq=%d Nk=%d B=%d" % (Nq, Nk, B)) if PROFILE_SHAPES else ""), 4.0 * B * Nq * Nk * C, 2.0 * B * C * (2 * Nq + 2 * Nk)):
         _check(lib().vd_attention_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, q.stride(1), k.stride(1),
                                       v.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
@@ -1435,6 +1447,24 @@ def freeu(h, skip, b, s):
     return h2, skip2
 
 
+def pag_fold(eps, reps, w):
+    """Fold the perturbed prediction of a perturbed-attention-guidance step into replica 0 (vd_pag_fold_f16, contract in
+    include/vd_hip.h): eps is fp16 [reps * B, ...] = [e_uncond ; e_cond ; e_perturbed] (reps 3) or [e_cond ; e_perturbed] (reps 2),
+    contiguous; w a device fp32 [1] (-s_pag / (s - 1), or s_pag).  In place, one launch.  Returns the view the step's update reads:
+    eps[:2 B] (the folded pair, the conditional replica untouched) for reps 3, eps[:B] for reps 2."""
+    _req(eps, "eps"); _req(w, "w", torch.float32)
+    if isinstance(reps, bool) or reps not in (2, 3):
+        raise VdHipError("pag_fold: reps must be 2 or 3, got %r" % (reps,))
+    if eps.dim() < 1 or eps.shape[0] < reps or eps.shape[0] % reps or eps.numel() == 0:
+        raise VdHipError("pag_fold: eps %s does not hold %d replicas of a batch" % (tuple(eps.shape), reps))
+    if w.numel() < 1:
+        raise VdHipError("pag_fold: w must hold one element")
+    n = eps.numel() // reps
+    with _Timed("pag_fold_kernel", 2.0 * n, 2.0 * n * (reps + 1)):
+        _check(lib().vd_pag_fold_f16(_ptr(eps), n, reps, _ptr(w), _stream()))
+    return eps[:(reps - 1) * (eps.shape[0] // reps)]
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1666,7 +1696,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "pag_fold", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
