@@ -698,6 +698,43 @@ int vd_attention_ident_f16(const void* q, const void* k, const void* v, void* ou
  * for a null pointer, n <= 0, reps outside {2, 3} or a misaligned eps / w.  Neither allocates nor synchronises (capturable). */
 int vd_pag_fold_f16(void* eps, int64_t n, int reps, const float* w, hipStream_t stream);
 
+/* Token merging for self-attention (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion", 2023; the tomesd package with
+ * sx = sy = 2, use_rand = False; not in the reference).  Four entry points (additive to ABI 8); none allocates or synchronises
+ * (capturable).  Every one returns < 0 (vd_last_error, the text starts with the entry's name) for null pointers, an empty problem,
+ * odd H or W, misaligned pointers, leading dimensions or sample strides, and r outside [0, Ns].
+ *
+ * Sets.  The tokens of a sample are n = y * W + x on its H x W grid (H, W even), N = H W.  Destinations: y and x both even, ordinal
+ * d = (y / 2) (W / 2) + x / 2, Nd = N / 4.  Sources: every other token in ascending n, ordinal i, Ns = 3 N / 4.
+ *
+ * vd_tome_match_f16: h is the metric, fp16 rows [C] at h + b * sample_stride + n * ldh (16-byte aligned, ldh and sample_stride
+ * multiples of 8), C in {32, 64, 128, 320, 640} (any other: < 0).  inv(n) = 1 / sqrt(sum_c h[n, c]^2) in fp32, 0 for an all-zero
+ * row.  For every source i:  score(i, d) = <h_i, h_d> inv(i) inv(d), the products of fp16 values accumulated in fp32
+ * (v_mfma_f32_32x32x16_f16; the score matrix never reaches memory); node_idx[b * Ns + i] = argmax_d score(i, d), among equal fp32
+ * values of dot * inv(d) the lowest d; node_max[b * Ns + i] = that score (the factor inv(i) is applied once, behind the argmax).
+ * The same input gives the same bits on every run.
+ *
+ * vd_tome_plan: rank[i] = #{j : node_max[j] > node_max[i], or node_max[j] == node_max[i] and j < i} per sample (a descending,
+ * stable order on the fp32 values; NaN must not occur); source i is merged iff rank[i] < r.  The merged tensor has N' = N - r rows:
+ * rows [0, Ns - r) are the unmerged sources, each at row rank[i] - r, rows [Ns - r, N') the destinations in ordinal order.
+ * row_of is int32 [B, N] per TOKEN: a destination's own row, an unmerged source's own row, for a merged source the row of
+ * destination node_idx[i].
+ *
+ * vd_tome_merge_f16: x fp16 [B, N, cols] (row n of sample b at x + b * sx + n * ldx; cols a multiple of 8, so a column slice of a
+ * fused projection is fine) -> out [B, N', cols] (ldo, so).  Unmerged source rows are bit-exact copies.  A destination row is the
+ * mean over itself and every source merged into it: the sum is EXACT (fp16 values are integers in units of 2^-24, summed as
+ * int64), the quotient is double(sum) / count, rounded ONCE to nearest even straight to fp16 (not double -> float -> half) -- so
+ * the result does not depend on the order of the members.  No atomics touch the data tensor.  Ns <= 12288 (grids up to 128 x 128),
+ * else < 0.
+ *
+ * vd_tome_unmerge_f16: out[b, n, :] = a[b, row_of[b, n], :] for the N tokens, a bit-exact gather of a [B, N', cols] (lda, sa). */
+int vd_tome_match_f16(const void* h, int ldh, int64_t sample_stride, int B, int H, int W, int C, int* node_idx, float* node_max,
+                      hipStream_t stream);
+int vd_tome_plan(const int* node_idx, const float* node_max, int B, int H, int W, int r, int* row_of, hipStream_t stream);
+int vd_tome_merge_f16(const void* x, int ldx, int64_t sx, int cols, const int* row_of, int B, int H, int W, int r, void* out,
+                      int ldo, int64_t so, hipStream_t stream);
+int vd_tome_unmerge_f16(const void* a, int lda, int64_t sa, int cols, const int* row_of, int B, int H, int W, int r, void* out,
+                        int ldo, int64_t so, hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # VD_BUILD_OUT: development builds of variants (VD_EXTRA_DEFS) next to the product library, for VD_HIP_LIB A/B runs
 OUT = os.environ.get("VD_BUILD_OUT") or os.path.join(HERE, "libvd_hip.so")
-SOURCES = ["gemm.hip", "conv_halo.hip", "conv_ups_phase.hip", "conv_wstream.hip", "ff_fused.hip", "ff_chain.hip", "gemm_row320.hip", "norm.hip", "gn_fused.hip", "attention.hip", "xattn_fused.hip", "elementwise.hip", "preprocess.hip", "lowrank.hip", "noise.hip", "unipc.hip", "window.hip", "freeu.hip", "pag.hip"]
+SOURCES = ["gemm.hip", "conv_halo.hip", "conv_ups_phase.hip", "conv_wstream.hip", "ff_fused.hip", "ff_chain.hip", "gemm_row320.hip", "norm.hip", "gn_fused.hip", "attention.hip", "xattn_fused.hip", "elementwise.hip", "preprocess.hip", "lowrank.hip", "noise.hip", "unipc.hip", "window.hip", "freeu.hip", "pag.hip", "tome.hip"]
 # every header under csrc/ (a kernel header that is not hashed would let a stale library pass the stamp check)
 import glob
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "vd_hip.h")]
@@ -32,6 +32,7 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "ff_fused.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
                "ff_chain.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
                "gemm_row320.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "tome.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # the DPM-Solver++ update (2M and SDE instances of one kernel): packed-fp32 forms of the unrolled 8-element
                # update duplicate every step scalar into a scalar register pair per use; with the inlined logf / sincospif of
                # the generator that spills 33 scalar registers.  The update's roundings are written out in the source, so

@@ -144,7 +144,7 @@ class CrossAttention(nn.Module, PackCache):
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
 
     def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False, repeat=1,
-                ident_from=None):
+                ident_from=None, tome=None):
         """ln_sums: row statistics of x for `ln` (from x's producer); out_sums: zeroed fp32 [rows, 2] the output projection
         accumulates the row statistics of ITS output into (for the LayerNorm in front of the next block part).
         defer_out: return the attention output `a` WITHOUT the output projection (the caller folds to_out + res into its next
@@ -155,8 +155,17 @@ class CrossAttention(nn.Module, PackCache):
         repeat > 1 (with a context; only with defer_out on the one-launch path, i.e. where vd_xattn_rep_f16 applies): x holds ONE
         replica of a classifier-free-guidance batch, context / kv all of them; the result has repeat times the samples of x.
         ident_from (self-attention only; perturbed-attention guidance): the samples from this index on take the identity attention
-        map, i.e. to_out(to_v(ln(x))) (ops.attention(ident_from=...)), whoever computed qkv."""
+        map, i.e. to_out(to_v(ln(x))) (ops.attention(ident_from=...)), whoever computed qkv.
+        tome (self-attention only; token merging, contract in include/vd_hip.h): None, or (H, W, r, metric[, sink]) with r > 0 --
+        the tokens are an H x W grid, metric [B, N, C] is the block's un-normalised input, and the r most redundant source tokens
+        are merged into their most similar destination: q | k | v as always -> ops.tome_match on the metric -> ops.tome_plan ->
+        ops.tome_merge of the fused q | k | v -> ops.attention on N - r rows -> ops.tome_unmerge back to N rows -> to_out.
+        sink, when given, is called with row_of (int32 [B, N]).  It does not combine with ident_from."""
         c = self.inner
+        if tome is not None and not (context is None and kv is None):
+            raise ops.VdHipError("CrossAttention(tome=...): token merging applies to self-attention only")
+        if tome is not None and ident_from is not None:
+            raise ops.VdHipError("CrossAttention(tome=..., ident_from=%r): token merging and the identity attention map do not combine" % (ident_from,))
         if ident_from is not None and not (context is None and kv is None):
             raise ops.VdHipError("CrossAttention(ident_from=%r): the identity attention map applies to self-attention only" % (ident_from,))
         if repeat > 1 and not (defer_out and (context is not None or kv is not None) and ln is not None and x.dim() == 3
@@ -174,7 +183,19 @@ class CrossAttention(nn.Module, PackCache):
                 if hip_layers.wstream_epi_level("qkv", x.numel() // x.shape[-1], x.shape[-1]):
                     kw["w_stream_epi"] = self._w_qkv_ln_stream(ln)
                 qkv = ops.linear(x, w, b, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums, **kw)
-            if ident_from is None:
+            if tome is not None:
+                tH, tW, r, metric = tome[:4]
+                if qkv.dim() != 3 or metric.dim() != 3 or metric.shape[:2] != qkv.shape[:2] or tH * tW != qkv.shape[1]:
+                    raise ops.VdHipError("CrossAttention(tome=...): the metric %s / q|k|v %s are not [B, %d x %d, *]"
+                                         % (tuple(metric.shape), tuple(qkv.shape), tH, tW))
+                node_idx, node_max = ops.tome_match(metric, tH, tW)
+                row_of = ops.tome_plan(node_idx, node_max, tH, tW, r)
+                if len(tome) > 4 and tome[4] is not None:
+                    tome[4](row_of)
+                m = ops.tome_merge(qkv, row_of, tH, tW, r)
+                a = ops.attention(m[..., :c], m[..., c:2 * c], m[..., 2 * c:], self.heads, scale=self.scale)
+                a = ops.tome_unmerge(a, row_of, tH, tW, r)
+            elif ident_from is None:
                 a = ops.attention(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, scale=self.scale)
             else:
                 a = ops.attention(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, scale=self.scale, ident_from=int(ident_from))
@@ -219,7 +240,8 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = LayerNorm(dim)
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
-    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None, ident_from=None):
+    def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None, ident_from=None,
+                tome=None):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
@@ -231,13 +253,17 @@ class BasicTransformerBlock(nn.Module):
         cross-attention and the chained tail -- read x / res through the batch period.  Only widths that have both kernels take
         repeat > 1 (period_consumers; C = 320): any other call is an error, the caller replicates in front of the block.  The result
         has repeat times the samples of x.
-        ident_from: handed to attn1 (CrossAttention.forward); the replicas then differ from attn1 on, so it needs repeat == 1."""
+        ident_from: handed to attn1 (CrossAttention.forward); the replicas then differ from attn1 on, so it needs repeat == 1.
+        tome: None, or (H, W, r, sink) of token merging: attn1 gets (H, W, r, x, sink) -- the metric is this block's un-normalised
+        input.  With repeat > 1 the merge runs on the one replica attn1 sees."""
+        if tome is not None:
+            tome = (tome[0], tome[1], tome[2], x, tome[3] if len(tome) > 3 else None)
         if ident_from is not None and repeat > 1:
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d, ident_from=%r): a perturbed replica cannot share attn1" % (repeat, ident_from))
         if repeat > 1 and not period_consumers(x.shape[-1], self.attn2.heads):
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d): width %d has no consumers with a batch period" % (repeat, x.shape[-1]))
         if hip_layers.LN_FOLD:  # the three LayerNorms ride in the q/k/v, q and GEGLU projections (VD_EPI_LNFOLD)
-            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from)
+            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome)
             C = x.shape[-1]
             fops = self.ff.chain_operands(self.norm3) if (x.is_contiguous() and ops.ff_geglu_supported(C)) else None
             if fops is not None and (ops.ff_chain_supported(C, "pre") or (post is not None and ops.ff_chain_supported(C, "post"))):
@@ -279,7 +305,7 @@ class BasicTransformerBlock(nn.Module):
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
             return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None), post=ff_post, sync=sync)
-        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from)
+        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome)
         x = self.attn2(self.norm2(x), context=context, res=x, kv=kv)
         x = self.ff(self.norm3(x), res=x)
         return x
@@ -311,7 +337,7 @@ class SpatialTransformer(nn.Module):
         and of the chained tail (vd.run_unet hands a guided batch over un-replicated only then)."""
         return period_consumers(self.proj_in.out_channels, self.transformer_blocks[0].attn2.heads)
 
-    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None):
+    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None):
         """Returns alpha * (proj_out(...) + bias) + res, res defaulting to x (the block's own skip).
         alpha/res implement VD's context mixing sum_i r_i * ST_i(x) without extra passes.
         sync: callable invoked right before the ONE launch that reads `res` (the last of the block): the caller runs the blocks
@@ -320,7 +346,11 @@ class SpatialTransformer(nn.Module):
         the entry and the self-attention run once per sample and the output has repeat times the samples of x (the block's own
         skip only: res is None).
         ident_from (perturbed-attention guidance, needs repeat == 1): samples [ident_from, B) of x take the identity self-attention
-        map in this block, whether q | k | v come from the chained entry kernel (width 320) or from the block's own projection."""
+        map in this block, whether q | k | v come from the chained entry kernel (width 320) or from the block's own projection.
+        tome: None, or (r, sink) of token merging (r > 0): this block's self-attention merges r tokens of its H x W grid, the metric
+        being the h that enters the transformer block (at width 320 the one the chained entry kernel returns)."""
+        if tome is not None:
+            tome = (x.shape[1], x.shape[2], int(tome[0]), tome[1] if len(tome) > 1 else None)
         assert repeat == 1 or ident_from is None, "a perturbed replica takes the replicated input"
         assert repeat == 1 or res is None, "a shared input takes the block's own skip"
         if repeat > 1 and not self.shares_cfg_head():
@@ -342,7 +372,7 @@ class SpatialTransformer(nn.Module):
             if pres.is_contiguous() and self.proj_out.out_channels == inner and self.proj_out.bias is not None:
                 wp, bp = self.proj_out._w()
                 post = (wp, bp, float(alpha), pres.view(B, H * W, C), H * W)
-            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from)
+            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome)
             if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the block's last launch
                 out = h[0]
                 st = ops.stats_of(out)
@@ -364,7 +394,8 @@ class SpatialTransformer(nn.Module):
             if pres.is_contiguous():   # proj_out rides in the feed-forward's output GEMM: that launch now is the one that reads res
                 ff_post = (self.proj_out, float(alpha), pres, H * W)
         h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
-                                       repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None, ident_from=ident_from)
+                                       repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None, ident_from=ident_from,
+                                       tome=tome)
         if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the feed-forward's output GEMM
             out = h[0]
             st = ops.stats_of(out)

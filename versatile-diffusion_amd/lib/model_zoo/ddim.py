@@ -21,7 +21,7 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import DeepCache, _freeu_arg, _pag_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable
+from .vd import DeepCache, _freeu_arg, _pag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable, tome_blocks
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -327,6 +327,9 @@ class DDIMSampler(object):
             raise ValueError("cache_interval > 1 does not combine with window: DeepCache would keep one feature per chunk of windows")
         # x_info['pag_scale'] / ['pag_layers'] (extension keys, vd._pag_arg): None, or (s_pag, layers); raises like the others
         pag = _pag_arg(x_info, self.model)
+        # x_info['tome_ratio'] / ['tome_max_downsample'] (extension keys, vd._tome_arg): None, or the TokenMerge; raises like the
+        # others.  The setting travels with every forward (_eps), like FreeU's
+        tome = _tome_arg(x_info, self.model, shape)
         # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
         c_info_list = _region_contexts(c_info_list, window, shape[0])
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
@@ -379,6 +382,10 @@ class DDIMSampler(object):
             intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
         if pag is not None:
             intermediates["pag_layers"] = pag[1]
+        if tome is not None:
+            th, tw = (x.shape[2], x.shape[3]) if window is None else window["key"][:2]
+            intermediates["tome_tokens"] = [(H * W, H * W - r) for _, H, W, r in
+                                            tome_blocks(self.model.diffuser[x_info["type"]], th, tw, tome)]
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
 
@@ -489,7 +496,9 @@ class DDIMSampler(object):
         window: the _window_state of a windowed call -- x is the canvas, and so is what comes back (_eps_windowed).
         x_info['freeu'] (FreeU, vd.freeu_setting) travels with every forward, so with windows it acts inside each window's.
         pag: None, or the layers of perturbed-attention guidance: one more replica, the last, runs those context blocks with
-        identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward."""
+        identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward.
+        x_info['tome_ratio'] / ['tome_max_downsample'] (token merging, vd._tome_arg) travel with every forward as apply_model*'s
+        'tome', so with windows the merge acts on each window's token grid."""
         if window is not None:
             assert deep is None, "DeepCache does not combine with windows"
             return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window, pag)
@@ -504,6 +513,9 @@ class DDIMSampler(object):
             xi["deep_cache"] = deep
         if x_info.get("freeu") is not None:
             xi["freeu"] = x_info["freeu"]
+        tome = _tome_arg(x_info, self.model)
+        if tome is not None:
+            xi["tome"] = tome
         if single:
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
@@ -570,13 +582,16 @@ class DDIMSampler(object):
         # and FreeU with its four values (b1, b2, s1, s2), None when off or all ones: the scalars are arguments of the captured
         # ops.freeu launches, and which stages launch at all depends on them -- one graph per setting;
         # and perturbed-attention guidance, (on?, layers): a graph captured with it runs one more replica, the identity attention of
-        # those context blocks and the fold; its scale is not in the key -- the fold's weight is loaded per call)
+        # those context blocks and the fold; its scale is not in the key -- the fold's weight is loaded per call;
+        # and token merging, (ratio, max_downsample) or None, in front of those two: r is an argument of the captured launches and
+        # decides the shapes behind them -- one graph per setting)
         pag = _pag_arg(x_info, self.model)
+        tome = _tome_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
         key = (id(self.model), wv, str(x.device), tuple(x.shape), x_info["type"], bool(guided), bool(single), bool(self.emb_hoist),
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
                inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"],
-               (pag is not None, None if pag is None else pag[1]), _freeu_arg(x_info))
+               None if tome is None else tome.key(), (pag is not None, None if pag is None else pag[1]), _freeu_arg(x_info))
         return key
 
     def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False):
@@ -658,6 +673,9 @@ class DDIMSampler(object):
         pag (None, or (s_pag, layers) of vd._pag_arg): the forward runs one more replica, perturbed, and ops.pag_fold folds its
         prediction into replica 0 between the forward and the update; the update, the rescale factors, the blend, the noise and the
         histories see the folded pair (or single) and nothing else, so every sampler on this loop gets it."""
+        tome = _tome_arg(x_info, self.model)
+        if tome is not None and tome.record is not None and self.use_graph:
+            raise ValueError("tome: TokenMerge.record is an eager-only hook; this loop captures its steps into a graph (use_graph)")
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
@@ -837,6 +855,7 @@ class DDIMSampler(object):
             raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows (or regions)")
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         pag = _pag_arg(x_info, self.model)      # so is perturbed-attention guidance: one more replica and the fold
+        _tome_arg(x_info, self.model, x_info["x"].shape)    # and token merging: the step's forward applies it (_eps)
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list, pag=pag is not None)
         x = x_info["x"]

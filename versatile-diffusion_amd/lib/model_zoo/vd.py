@@ -400,7 +400,121 @@ def _pag_fwd_arg(x_info, net):
     return pag_layers(pag[0], net), int(row0)
 
 
-def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None):
+# ---- token merging (x_info['tome_ratio'], x_info['tome_max_downsample']; forward key x_info['tome']) ---------------------------
+# Bolya & Hoffman, "Token Merging for Fast Stable Diffusion" (2023); tomesd.apply_patch(model, ratio, max_downsample) with
+# sx = sy = 2 and use_rand = False.  In the context blocks whose token grid is the latent grid (or, max_downsample = 2, half of it
+# per side) the self-attention runs on N - r tokens: CrossAttention.forward(tome=...), contract in include/vd_hip.h.
+class TokenMerge(object):
+    """The setting of token merging: ratio, a real number in [0, 0.75] (0 = off), and max_downsample, 1 or 2.  ValueError (matching
+    'tome') for anything else.  record: None, or a list that receives (walk index of the context block, row_of.clone()) from every
+    merging block of every forward -- an eager-only test hook, a ValueError under graph capture."""
+
+    def __init__(self, ratio, max_downsample=1):
+        if isinstance(ratio, (bool, np.bool_)) or not isinstance(ratio, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(ratio)) or not 0. <= float(ratio) <= 0.75:
+            raise ValueError("tome_ratio must be a real number in [0, 0.75], got %r" % (ratio,))
+        if isinstance(max_downsample, (bool, np.bool_)) or not isinstance(max_downsample, (int, np.integer)) \
+                or int(max_downsample) not in (1, 2):
+            raise ValueError("tome_max_downsample must be 1 or 2, got %r" % (max_downsample,))
+        self.ratio = float(ratio)
+        self.max_downsample = int(max_downsample)
+        self.record = None
+
+    def key(self):
+        return self.ratio, self.max_downsample
+
+    def r(self, H, W):
+        """How many of the H W tokens of a merging block are merged: min(int(N ratio), Ns), Ns = 3 N / 4."""
+        N = int(H) * int(W)
+        return min(int(N * self.ratio), N - N // 4)
+
+
+def tome_blocks(net, H0, W0, tm):
+    """[(walk index of the context block, H, W, r)] of the blocks of the 2-D data net `net` that merge under the TokenMerge `tm` on
+    an H0 x W0 latent, in walk order (a block after k Downsamples has the grid H0 / 2^k x W0 / 2^k).  ValueError (matching
+    'tome') for a net without such a walk and for a merging level whose grid is odd on a side."""
+    from .openaimodel import Downsample, UNetModel0D_Next, Upsample
+    if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("i_order", "m_order", "o_order", "data_blocks")):
+        raise ValueError("tome needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+    d_iter = iter(net.data_blocks)
+    level, ci, out = 0, 0, []
+    for s in list(net.i_order) + list(net.m_order) + list(net.o_order):
+        if s == "d":
+            blk = next(d_iter)
+            if any(isinstance(m, Downsample) for m in blk.modules()):
+                level += 1
+            elif any(isinstance(m, Upsample) for m in blk.modules()):
+                level -= 1
+        elif s == "c":
+            if 2 ** level <= tm.max_downsample:
+                f = 2 ** level
+                if H0 % (2 * f) or W0 % (2 * f):
+                    raise ValueError("tome: a %d x %d latent (or window) leaves the merging level %d with an odd token grid; both "
+                                     "sides must be multiples of %d" % (H0, W0, level, 2 * f))
+                H, W = H0 // f, W0 // f
+                if tm.r(H, W) > 0:
+                    out.append((ci, H, W, tm.r(H, W)))
+            ci += 1
+    return out
+
+
+def _tome_arg(x_info, model, shape=None):
+    """The sampler keys of token merging validated: None when x_info['tome_ratio'] is absent, None or 0 (off: today's call), else the
+    TokenMerge(ratio, x_info.get('tome_max_downsample', 1)).  x_info['tome'] may hold a ready TokenMerge instead (the way to set its
+    `record` hook on a sampler call).  ValueError (matching 'tome') for a bool, a non-number or a ratio outside [0, 0.75], a
+    max_downsample other than 1 or 2, another flow than the 2-D image flow, perturbed-attention guidance in the same call (identity-map
+    replicas are out of scope) and, when `shape` ([B, C, H, W]) is given, a latent -- or with x_info['window'] a window -- side that
+    leaves a merging level with an odd grid.  Touches no device."""
+    tm = x_info.get("tome")
+    if tm is not None and not isinstance(tm, TokenMerge):
+        raise ValueError("x_info['tome'] must be a TokenMerge, got %r" % (tm,))
+    if tm is not None and x_info.get("tome_ratio") is not None:
+        raise ValueError("x_info holds both 'tome' and 'tome_ratio': pass one")
+    if tm is None:
+        ratio = x_info.get("tome_ratio")
+        if ratio is None:
+            if x_info.get("tome_max_downsample") is not None:
+                TokenMerge(0., x_info["tome_max_downsample"])
+            return None
+        tm = TokenMerge(ratio, x_info.get("tome_max_downsample", 1))
+    if tm.ratio == 0.:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("tome_ratio applies to x_info['type'] == 'image' only (self-attention over a token grid), got %r"
+                         % (x_info.get("type"),))
+    if _pag_arg(x_info, model) is not None or x_info.get("pag") is not None:
+        raise ValueError("tome_ratio with pag_scale is out of scope on purpose: token merging and identity-map replicas do not combine")
+    if shape is not None:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 4:
+            raise ValueError("tome: the latent shape must be [B, C, H, W], got %s" % (shape,))
+        H, W = shape[2:]
+        if x_info.get("window") is not None:
+            from . import windows
+            h, w = windows.int_pair("window", x_info["window"])
+            H, W = min(h, H), min(w, W)
+        tome_blocks(model.diffuser[x_info["type"]], H, W, tm)
+    return tm
+
+
+def _tome_fwd_arg(x_info):
+    """x_info['tome'] (extension key of apply_model*, set by the samplers) validated: None (absent, or ratio 0), or the TokenMerge."""
+    tm = x_info.get("tome")
+    if tm is None:
+        return None
+    if not isinstance(tm, TokenMerge):
+        raise ValueError("x_info['tome'] must be a TokenMerge, got %r" % (tm,))
+    if tm.ratio == 0.:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("tome applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if x_info.get("pag") is not None:
+        raise ValueError("tome with pag is out of scope on purpose: token merging and identity-map replicas do not combine")
+    return tm
+
+
+def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None,
+             tome=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -424,7 +538,20 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     (SpatialTransformer.forward(ident_from=...)); a half-batch branch holding samples [b0, b1) gets clamp(row0 - b0, 0, b1 - b0).
     A forward with pag replicates h IN FRONT of the first context block (share = 1): the shared CFG head is not used, whichever
     layers are named, so block 0 can be a perturbed layer and a perturbed replica never reads a shared self-attention.  It does
-    not combine with deep (ValueError)."""
+    not combine with deep (ValueError).
+    tome: None, or a TokenMerge with ratio > 0: the context blocks of tome_blocks (every context type's block at those walk
+    indices) merge r tokens in their self-attention (SpatialTransformer.forward(tome=(r, sink))); with its `record` set every such
+    block appends (walk index, row_of.clone()) -- not under graph capture (ValueError).  It does not combine with pag (ValueError)."""
+    tmap = None
+    if tome is not None:
+        if x.dim() != 4:
+            raise ValueError("tome needs a 2-D data net (x_info['type'] == 'image')")
+        if pag is not None:
+            raise ValueError("tome does not combine with pag")
+        if tome.record is not None and x.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise ValueError("tome: TokenMerge.record is an eager-only hook, this forward is being captured into a graph")
+        tmap = {ci: r for ci, _, _, r in tome_blocks(data_net, x.shape[-2], x.shape[-1], tome)}
+        tmap = (tmap, tome.record) if tmap else None
     if pag is not None:
         if x.dim() != 4:
             raise ValueError("pag needs a 2-D data net (x_info['type'] == 'image')")
@@ -476,15 +603,18 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None):
+    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
         repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them.
-        ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag)."""
+        ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag).
+        tome: None, or (r, sink) of token merging for these blocks' self-attention."""
         single = len(modules) == 1
         pkw = {} if ident_from is None else {"ident_from": int(ident_from)}
+        if tome is not None:
+            pkw["tome"] = tome
         if repeat > 1:
             assert single and sl is None and ident_from is None
-            return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat)
+            return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat, **pkw)
         kvs = [context_kv(m, sp) for m, sp in zip(modules, specs)]
         if sl is not None:
             kvs = [None if kv is None else kv[sl[0]:sl[1]] for kv in kvs]
@@ -538,7 +668,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
                               h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
-                              fmap or None, pag)
+                              fmap or None, pag, tmap)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -579,9 +709,10 @@ def _fork_region(steps, hw0, thr):
 
 
 def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None,
-                   pag=None):
+                   pag=None, tome=None):
     """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
-    the active FreeU stages.  pag: None, or (layers, row0) of run_unet."""
+    the active FreeU stages.  pag: None, or (layers, row0) of run_unet.  tome: None, or ({walk index of a merging context block: r},
+    the TokenMerge's record list or None)."""
     state = {"shared": shared}
 
     def walk(lo, hi, h, hs, sl=None):
@@ -611,6 +742,9 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 if pag is not None and st[4] in pag[0]:
                     b0, b1 = (0, h.shape[0]) if sl is None else sl
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, ident_from=min(max(pag[1] - b0, 0), b1 - b0))
+                elif tome is not None and st[4] in tome[0]:
+                    sink = None if tome[1] is None else (lambda row_of, ci=st[4], rec=tome[1]: rec.append((ci, row_of.clone())))
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, tome=(tome[0][st[4]], sink))
                 else:
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
             elif st[0] == "save":
@@ -842,10 +976,11 @@ class VD_v2_0(nn.Module):
         deep = _deep_arg(x_info)        # extension key: (DeepCache, "store" | "reuse"), see run_unet
         freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])   # extension key: (layers, row0), see run_unet
+        tome = _tome_fwd_arg(x_info)    # extension key: a TokenMerge, see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag).to(x.dtype)
+                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -856,9 +991,11 @@ class VD_v2_0(nn.Module):
         deep = _deep_arg(x_info)
         freeu = _freeu_arg(x_info)
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])
+        tome = _tome_fwd_arg(x_info)
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
         specs = [(self.diffuser[ci["type"]].context_blocks, self._prep(ci["c"]), ci["ratio"], ci.get("kv_cache"))
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
-                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag).to(x.dtype)
+                        repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag,
+                        tome=tome).to(x.dtype)

@@ -1465,6 +1465,83 @@ def pag_fold(eps, reps, w):
     return eps[:(reps - 1) * (eps.shape[0] // reps)]
 
 
+TOME_WIDTHS = (32, 64, 128, 320, 640)      # the metric widths vd_tome_match_f16 has an instance for
+
+
+def _tome_rows(t, name):
+    """A [B, rows, cols] fp16 GPU view with unit inner stride (column slices of a fused projection and batch slices included)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float16 or t.dim() != 3 or t.stride(-1) != 1:
+        raise VdHipError("%s must be a 3-d fp16 GPU tensor with unit inner stride" % name)
+
+
+def _tome_grid(B, N, H, W, what):
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H * W != N:
+        raise VdHipError("%s: the grid %r x %r does not hold the %d rows of a sample" % (what, H, W, N))
+
+
+def tome_match(h, H, W):
+    """Token-merging match (vd_tome_match_f16, contract in include/vd_hip.h): h [B, H W, C] fp16, the metric -> (node_idx int32
+    [B, Ns], node_max fp32 [B, Ns]): for every source token its most similar destination and the cosine score.  One launch."""
+    _tome_rows(h, "h")
+    B, N, C = h.shape
+    _tome_grid(B, N, H, W, "tome_match")
+    Ns = N - N // 4
+    idx = torch.empty((B, Ns), dtype=torch.int32, device=h.device)
+    mx = torch.empty((B, Ns), dtype=torch.float32, device=h.device)
+    with _Timed("tome_match_kernel<%d>" % C, 2.0 * B * Ns * (N // 4) * C, 2.0 * B * N * C):
+        _check(lib().vd_tome_match_f16(_ptr(h), h.stride(1), h.stride(0), B, H, W, C, _ptr(idx), _ptr(mx), _stream()))
+    return idx, mx
+
+
+def tome_plan(node_idx, node_max, H, W, r):
+    """Token-merging plan (vd_tome_plan): ranks the sources by score (descending, stable) and returns row_of int32 [B, H W], the
+    row of the merged [B, H W - r, *] tensor every token reads its attention output from.  One launch."""
+    _req(node_idx, "node_idx", torch.int32); _req(node_max, "node_max", torch.float32)
+    B = node_idx.shape[0]
+    N = H * W
+    if node_idx.dim() != 2 or tuple(node_max.shape) != tuple(node_idx.shape) or node_idx.shape[1] != N - N // 4:
+        raise VdHipError("tome_plan: node_idx %s / node_max %s are not [B, Ns] of a %d x %d grid" % (tuple(node_idx.shape), tuple(node_max.shape), H, W))
+    row_of = torch.empty((B, N), dtype=torch.int32, device=node_idx.device)
+    with _Timed("tome_plan_kernel", 2.0 * B * (N - N // 4) ** 2, 12.0 * B * N):
+        _check(lib().vd_tome_plan(_ptr(node_idx), _ptr(node_max), B, H, W, int(r), _ptr(row_of), _stream()))
+    return row_of
+
+
+def tome_merge(x, row_of, H, W, r):
+    """Token-merging merge (vd_tome_merge_f16): x [B, H W, cols] fp16 -> [B, H W - r, cols], contiguous: unmerged sources copied,
+    every destination the exact mean over itself and the sources merged into it, rounded once to fp16.  One launch."""
+    _tome_rows(x, "x"); _req(row_of, "row_of", torch.int32)
+    B, N, cols = x.shape
+    _tome_grid(B, N, H, W, "tome_merge")
+    if tuple(row_of.shape) != (B, N):
+        raise VdHipError("tome_merge: row_of %s is not [%d, %d]" % (tuple(row_of.shape), B, N))
+    out = torch.empty((B, N - int(r), cols), dtype=torch.float16, device=x.device)
+    with _Timed("tome_merge_kernel", 1.0 * B * N * cols, 4.0 * B * N * cols):
+        _check(lib().vd_tome_merge_f16(_ptr(x), x.stride(1), x.stride(0), cols, _ptr(row_of), B, H, W, int(r), _ptr(out), out.stride(1),
+                                       out.stride(0), _stream()))
+    return out
+
+
+def tome_unmerge(a, row_of, H, W, r, out=None):
+    """Token-merging unmerge (vd_tome_unmerge_f16): a [B, H W - r, cols] fp16 -> [B, H W, cols]: out[b, n] = a[b, row_of[b, n]],
+    a bit-exact row gather.  One launch."""
+    _tome_rows(a, "a"); _req(row_of, "row_of", torch.int32)
+    B, Nm, cols = a.shape
+    N = H * W
+    if Nm != N - int(r) or tuple(row_of.shape) != (B, N):
+        raise VdHipError("tome_unmerge: a %s / row_of %s do not fit a %d x %d grid with r = %d" % (tuple(a.shape), tuple(row_of.shape), H, W, r))
+    if out is None:
+        out = torch.empty((B, N, cols), dtype=torch.float16, device=a.device)
+    else:
+        _tome_rows(out, "out")
+        if tuple(out.shape) != (B, N, cols):
+            raise VdHipError("tome_unmerge: out %s is not [%d, %d, %d]" % (tuple(out.shape), B, N, cols))
+    with _Timed("tome_unmerge_kernel", 0.0, 4.0 * B * N * cols):
+        _check(lib().vd_tome_unmerge_f16(_ptr(a), a.stride(1), a.stride(0), cols, _ptr(row_of), B, H, W, int(r), _ptr(out), out.stride(1),
+                                         out.stride(0), _stream()))
+    return out
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1696,7 +1773,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "pag_fold", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
