@@ -626,6 +626,38 @@ int vd_window_merge_masked_f16(const void* eps_win, float* acc, void* eps, const
                                const float* inv_den, const int32_t* offs, int RB, int C, int H, int W, int h, int w, int slots,
                                int valid, int wrap, int first, int last, hipStream_t stream);
 
+/* Tiled VAE decode / encode (not in the reference; tables: lib/model_zoo/vae_tiles.py on lib/model_zoo/windows.py): the KL-f8
+ * autoencoder runs on overlapping tiles of a canvas, every tile a sample of its own, and vd_tile_blend_f16 (additive to ABI 8)
+ * fuses the tiles' outputs into the canvas -- weighted sum, normalisation, affine, clamp and layout change in one pass.
+ *   tiles   fp16 [RB, slots, ph, pw, C]  channels-last, as the decoder (C = 3) / quant_conv (C = 2 zc) leave them; batch order
+ *                                        (sample, slot); one chunk of the call's tiles
+ *   acc     fp32 [RB, C, PH, PW]         the running sum, exact between launches; may be NULL only when first && last
+ *   out     fp16 [RB, C, PH, PW] (out_nhwc == 0) or [RB, PH, PW, C] (out_nhwc != 0); written only when last (else may be NULL)
+ *   wgt     fp32 [ph, pw], inv_den fp32 [PH, PW], offs int32 [slots][2] rows {oy_k, ox_k} in the units of the canvas being
+ *           written, all in DEVICE memory
+ * One work item owns one canvas pixel (rb, Y, X) with all its C channels -- a gather: no atomics, a fixed order.  Per element:
+ *   a = first ? 0 : acc[...]
+ *   for k = 0 .. valid-1 ascending, if tile k covers the pixel at (i, j) = (Y - oy_k, X - ox_k [+ PW when wrap and that
+ *   is negative: the column mod PW for 0 <= ox_k < PW]):
+ *       a = fmaf(wgt[i, j], (float)tiles[rb, k, i, j, c], a)
+ *   acc[...] = a  unless first && last
+ *   if last:
+ *       v = a * inv_den[Y, X]                       one fp32 multiply, rounded to fp32
+ *       v = fmaf(v, scale, shift)
+ *       if clamp01: v = fminf(fmaxf(v, 0), 1)       (a NaN comes out as 0, as fmaxf has it)
+ *       out[...] = fp16(v)                          one rounding to fp16
+ * The decode uses (scale, shift, clamp01) = (0.5, 0.5, 1) and NCHW out (the image in [0, 1]); the encode (1, 0, 0) and
+ * channels-last out (the moments).  Slots >= valid are never read.  The chain runs in ascending tile order and acc is exact fp32
+ * between launches, so the result has the same bits however the tiles are split into launches.  The C fp16 of a tile pixel are
+ * read (and a channels-last pixel written) with accesses of up to 16 bytes when C is even and the buffers start on such a
+ * boundary, else one by one: the same elements, the same bits.
+ * Neither allocates nor synchronises.  Returns < 0 (vd_last_error) for null pointers (acc and out as above), non-positive sizes,
+ * ph > PH or pw > PW, valid outside [1, slots] and C outside [1, 16].  The offsets are NOT validated (windows.window_offsets
+ * builds them); coverage is tested from the pixel's side, so no table makes the kernel leave its buffers. */
+int vd_tile_blend_f16(const void* tiles, float* acc, void* out, const float* wgt, const float* inv_den, const int32_t* offs,
+                      int RB, int C, int PH, int PW, int ph, int pw, int slots, int valid, int wrap, int first, int last,
+                      int out_nhwc, float scale, float shift, int clamp01, hipStream_t stream);
+
 /* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024; not in the reference) at one skip concatenation of the
  * UNet's decoder.  The setting is four real numbers (b1, b2, s1, s2).  With W1 the width of the widest h that enters any
  * output-stage block of the 2-D data net and W2 = W1 / 2 (integer), a skip load whose entering h [B, H, W, C0] has C0 == W1 is

@@ -77,7 +77,7 @@ def _cache_args(x_info, model):
 def _window_args(x_info, shape, model):
     """The plan of a windowed (MultiDiffusion) call from x_info's extension keys, or None: `window` (an int or (h, w) in latent
     pixels; absent = off), `window_stride` (an int or a pair, default half the window per axis), `window_wrap` (bool, default
-    False: the x axis wraps around, a 360-degree panorama), `window_weight` ('uniform', the default, or 'gaussian') and
+    False: the x axis wraps around, a 360-degree panorama), `window_weight` ('uniform', the default, 'gaussian' or 'tent') and
     `window_batch` (an int >= 1, default 8: the most windows per sample in one UNet forward).  Validated with the tables of
     lib/model_zoo/windows.py: ValueError for a bad value of any key and for a flow other than the 2-D image flow.  None also
     when the plan has a single window (window == canvas): that call is the plain call and gives its bits.  The plan: the

@@ -97,7 +97,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                       images=None, fidelity=0., device_generator=False, mask=None, guidance_rescale=0.,
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
                       window_weight="uniform", window_batch=8, freeu=None, region_masks=None, pag_scale=None,
-                      pag_layers=None, tome_ratio=None, tome_max_downsample=None):
+                      pag_layers=None, tome_ratio=None, tome_max_downsample=None, vae_tile=None, vae_tile_stride=None,
+                      vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -130,9 +131,16 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     region_masks: the samplers' x_info['region_masks'] (regional prompts on the windowed path, ddim._window_args; None = off, and
     then the key is not set; it needs `window`).  A context's 'conditioning' may then be a list of one [B, L, D] tensor per
-    region, sliced per sample (_slice_ctx).  The masks are shared by the samples, so every rank sees the same ones."""
+    region, sliced per sample (_slice_ctx).  The masks are shared by the samples, so every rank sees the same ones.
+
+    vae_tile, vae_tile_stride, vae_tile_wrap, vae_tile_weight, vae_tile_batch: the autoencoder's tile, tile_stride, tile_wrap,
+    tile_weight and tile_batch (the tiled VAE path, lib/model_zoo/vae_tiles.py), passed to both net.vae_encode and
+    net.vae_decode; None = the key is not passed, and with all five None the calls are the plain ones.  Tiles lie on a
+    sample's H and W, so a rank's slice decodes to what the whole batch would."""
     if mask is not None and images is None:
         raise ValueError("vd_sample_sharded: mask needs images")
+    vae_keys = {k: v for k, v in (("tile", vae_tile), ("tile_stride", vae_tile_stride), ("tile_wrap", vae_tile_wrap),
+                                  ("tile_weight", vae_tile_weight), ("tile_batch", vae_tile_batch)) if v is not None}
 
     def sample_fn(x_T, ctxs):
         for ci in ctxs:
@@ -148,7 +156,7 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             rank = dist.get_rank(group) if dist.is_initialized() else 0
             lo, hi = shard_bounds(shape[0], world, rank)
             post = draw_initial_latent(shape, int(seed) + 1)[lo:hi].to(x_T.device)
-            x0 = net.vae_encode(images, which="image", noise=post)
+            x0 = net.vae_encode(images, which="image", noise=post, **vae_keys)
             x_info = {"type": "image", "x0": x0, "x0_noise": x_T}
             if fidelity > 0.:
                 x_info["x0_forward_timesteps"] = int(steps * (1 - fidelity))
@@ -187,5 +195,5 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                                                verbose=False)
         return z
 
-    return sample_sharded(sample_fn, lambda z: net.vae_decode(z, which="image"), shape, c_info_list, seed, net.device,
+    return sample_sharded(sample_fn, lambda z: net.vae_decode(z, which="image", **vae_keys), shape, c_info_list, seed, net.device,
                           group=group, device_generator=device_generator)

@@ -57,7 +57,10 @@ def window_offsets(H, W, window, stride, wrap=False, multiple=1):
 def window_weights(h, w, kind):
     """fp32 [h, w]: the weight of each pixel of a window in the fusion.  'uniform': ones (MultiDiffusion).  'gaussian': the
     outer product of g(i) = exp(-((i - (n - 1) / 2) / n)^2 / (2 * 0.01)) per axis of length n (the Mixture-of-Diffusers weighting;
-    its normalisation cancels against window_inv_den), computed in float64 and rounded once."""
+    its normalisation cancels against window_inv_den), computed in float64 and rounded once.  'tent': the outer product of
+    t(i) = min(i + 1, n - i) per axis, small integers and so exact in fp32 (the tiled VAE's default, lib/model_zoo/vae_tiles.py):
+    a tile's weight falls to its minimum at the tile's edge, so weight / denominator is continuous across tile edges where
+    uniform averaging leaves a step."""
     h, w = _int("h", h), _int("w", w)
     if h < 1 or w < 1:
         raise ValueError("window_weights: h and w must be >= 1, got %r" % ((h, w),))
@@ -66,7 +69,10 @@ def window_weights(h, w, kind):
     if kind == "gaussian":
         g = lambda n: np.exp(-((np.arange(n, dtype=np.float64) - (n - 1) / 2.0) / n) ** 2 / (2 * 0.01))
         return np.outer(g(h), g(w)).astype(np.float32)
-    raise ValueError("window_weight must be 'uniform' or 'gaussian', got %r" % (kind,))
+    if kind == "tent":
+        t = lambda n: np.minimum(np.arange(n) + 1, n - np.arange(n)).astype(np.float64)
+        return np.outer(t(h), t(w)).astype(np.float32)
+    raise ValueError("window_weight must be 'uniform', 'gaussian' or 'tent', got %r" % (kind,))
 
 
 def window_inv_den(H, W, offsets, weights, wrap):

@@ -1360,6 +1360,49 @@ def window_merge_masked(eps_win, offs, wgt, mask, inv_den, H, W, valid, wrap, fi
     return out if last else acc
 
 
+def tile_blend(tiles, offs, wgt, inv_den, PH, PW, valid, wrap, first, last, acc=None, out=None, out_nhwc=False, scale=1.0,
+               shift=0.0, clamp01=False):
+    """One launch of the fusion of a tiled VAE pass (vd_tile_blend_f16 in include/vd_hip.h): tiles fp16 [RB, slots, ph, pw, C]
+    channels-last (a chunk of the decoder's or quant_conv's per-tile outputs), offs device int32 [slots, 2] in canvas units, wgt
+    fp32 [ph, pw], inv_den fp32 [PH, PW]; the first `valid` slots are summed in ascending order onto acc (fp32 [RB, C, PH, PW];
+    started at 0 when `first`), and when `last` out = fp16(clamp(fma(acc * inv_den, scale, shift))) as [RB, C, PH, PW], or
+    [RB, PH, PW, C] with `out_nhwc`.  acc is needed unless first and last.  Returns out when `last`, else acc."""
+    PH, PW, valid, first, last, out_nhwc = int(PH), int(PW), int(valid), bool(first), bool(last), bool(out_nhwc)
+    _req(tiles, "tiles"); _req(wgt, "wgt", torch.float32); _req(inv_den, "inv_den", torch.float32)
+    slots = _window_table(offs)
+    if tiles.dim() != 5 or tiles.shape[1] != slots:
+        raise VdHipError("tiles has shape %s, expected [RB, %d, ph, pw, C]" % (tuple(tiles.shape), slots))
+    RB, _, ph, pw, C = tiles.shape
+    if not 1 <= C <= 16:
+        raise VdHipError("C = %d outside [1, 16]" % C)
+    if not (1 <= ph <= PH and 1 <= pw <= PW):
+        raise VdHipError("a tile of %d x %d does not fit the canvas %d x %d" % (ph, pw, PH, PW))
+    if tuple(wgt.shape) != (ph, pw):
+        raise VdHipError("wgt has shape %s, expected %s" % (tuple(wgt.shape), (ph, pw)))
+    if tuple(inv_den.shape) != (PH, PW):
+        raise VdHipError("inv_den has shape %s, expected %s" % (tuple(inv_den.shape), (PH, PW)))
+    if not 1 <= valid <= slots:
+        raise VdHipError("valid = %d outside [1, %d]" % (valid, slots))
+    canvas = (RB, C, PH, PW)
+    if acc is None and not (first and last):
+        if not first:
+            raise VdHipError("acc is needed to continue a sum (first is False)")
+        acc = torch.empty(canvas, device=tiles.device, dtype=torch.float32)
+    _req(acc, "acc", torch.float32)
+    if acc is not None and tuple(acc.shape) != canvas:
+        raise VdHipError("acc has shape %s, expected %s" % (tuple(acc.shape), canvas))
+    oshape = (RB, PH, PW, C) if out_nhwc else canvas
+    if last and out is None:
+        out = torch.empty(oshape, device=tiles.device, dtype=torch.float16)
+    _req(out, "out")
+    if out is not None and tuple(out.shape) != oshape:
+        raise VdHipError("out has shape %s, expected %s" % (tuple(out.shape), oshape))
+    _check(lib().vd_tile_blend_f16(_ptr(tiles), _ptr(acc), _ptr(out), _ptr(wgt), _ptr(inv_den), _ptr(offs), RB, C, PH, PW, ph,
+                                   pw, slots, valid, int(bool(wrap)), int(first), int(last), int(out_nhwc), float(scale),
+                                   float(shift), int(bool(clamp01)), _stream()))
+    return out if last else acc
+
+
 _freeu_tables = {}
 _freeu_lock = threading.Lock()
 
@@ -1773,7 +1816,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
