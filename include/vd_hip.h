@@ -730,6 +730,50 @@ int vd_attention_ident_f16(const void* q, const void* k, const void* v, void* ou
  * for a null pointer, n <= 0, reps outside {2, 3} or a misaligned eps / w.  Neither allocates nor synchronises (capturable). */
 int vd_pag_fold_f16(void* eps, int64_t n, int reps, const float* w, hipStream_t stream);
 
+/* Self-attention guidance (Hong et al., "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance", ICCV 2023;
+ * diffusers' StableDiffusionSAGPipeline(sag_scale); not in the reference).  A step reads the self-attention map of the middle
+ * context block, blurs the pixels of its data prediction that the map attends to, re-noises the result, predicts a second time
+ * from that degraded latent (e_d) and combines, with e0 the first forward's replica 0 (e_u when guided, else e_c),
+ *     e = e_u + s (e_c - e_u) + s_sag (e0 - e_d)        (unguided, s == 1:  e = e_c + s_sag (e_c - e_d)).
+ * Three entry points (additive to ABI 8); none allocates or synchronises (capturable).  Each returns < 0 (vd_last_error, the text
+ * starts with the entry's name) for null or misaligned pointers, an empty problem and what is listed with it.
+ *
+ * vd_sag_mass_f16 (the attention map and `attn_map.mean(1).sum(1)` of diffusers' sag_masking): q and k are fp16 with the leading
+ * dimensions ldq / ldk and the sample strides sq / sk of vd_attention_f16 (column slices of one fused [B, N, 3 C] projection and
+ * contiguous batch-slice views included; 16-byte aligned, strides multiples of 8); head h reads the columns [h D, (h + 1) D).
+ * With s(i, j) = scale * sum_d q[i, d] k[j, d] (the products of fp16 values summed in fp32 in ascending d, one fp32 multiplication
+ * by scale) and P[i, j] = exp(s(i, j) - max_j s) / sum_j exp(s(i, j) - max_j s), all fp32 -- P is never rounded to fp16 --
+ *     mass[b * N + j] = (1 / H) * sum_h sum_i P[b, h, i, j]          fp32 [B][N]: the sum over QUERIES, per KEY, the mean over heads.
+ * Two passes per head (row maximum and row sum of every query; then the scores again, summed per key), every sum in a fixed
+ * order: no float atomics, the same input gives the same bits on every run.  D as vd_attention_f16: 40, 64, 80, 160, or one head
+ * of 128 / 256 / 512 (any other: < 0).  N <= 1024 (more: < 0).
+ *
+ * vd_sag_degrade_f16 (the mask and interpolate of sag_masking, gaussian_blur_2d, pred_x0 and add_noise for an epsilon model, in
+ * ONE launch): x, eps0, xd are fp16 [B, C, H, W]; mass fp32 [T][B][Hm Wm] (one map per context type); ratio fp32 [T]; taps fp32
+ * [9] (the normalised Gaussian, g[k] ~ exp(-((k - 4) / sigma)^2 / 2)); coef fp32 [3] = {sa, s1, isa} = {sqrt(a_t), sqrt(1 - a_t),
+ * 1 / sqrt(a_t)} -- all DEVICE operands, so one captured launch serves every step, scale and sigma.  Per sample b, all in fp32:
+ *     m[j]       = fmaf(ratio[t], mass[t][b][j], m[j])  for t ascending, from 0
+ *     M(y, x)    = m[((y * Hm) / H) * Wm + (x * Wm) / W] > 1.0            strict; nearest neighbour in integers; every channel alike
+ *     p0(y, x)   = fmaf(-s1, eps0, x) * isa                               one fma, one multiplication
+ *     row(y, x)  = sum_j g[j] p0(y, refl(x + j - 4, W))                   nine fmas from 0, j ascending
+ *     blur(y, x) = sum_i g[i] row(refl(y + i - 4, H), x)                  nine fmas from 0, i ascending
+ *     d          = M ? blur : p0
+ *     xd         = fp16(fmaf(sa, d, s1 * eps0))                           a rounding of its own, to nearest even
+ * refl is torch's "reflect" padding, without edge repeat (-1 -> 1, n -> n - 2): H, W >= 5 (less: < 0).  A 32 x 32 tile of a plane
+ * with its 4-pixel halo of p0 is staged in LDS; a tile without a masked pixel skips the blur (the same bits: d = p0).
+ *
+ * vd_sag_fold_f16: eps is fp16, its leading [n] replica 0 of the step's prediction; e_d fp16 [n]; w a fp32[1] in DEVICE memory.
+ *     a = fp16(fmaf(w, fp32(a) - fp32(e_d), fp32(a)))        one fp32 subtraction, one fma, a rounding of its own to fp16
+ * in place on the leading [n]; nothing else is written, and w == 0 writes nothing (replica 0 keeps its bits).  Guided: the host
+ * loads w = -s_sag / (s - 1), formed in double and rounded once to fp32, so the update's a' + s (e_c - a') is the formula above and
+ * every fused update vd_cfg_*_step_* and vd_cfg_rescale_factor_f16 run unchanged; unguided: w = s_sag.  16-byte accesses when eps
+ * and e_d are 16-byte aligned and n is a multiple of 8, else one element per lane with the same arithmetic.  n <= 0: < 0. */
+int vd_sag_mass_f16(const void* q, const void* k, float* mass, int B, int H, int N, int D, int ldq, int ldk, int64_t sq,
+                    int64_t sk, float scale, hipStream_t stream);
+int vd_sag_degrade_f16(const void* x, const void* eps0, const float* mass, const float* ratio, int T, const float* taps,
+                       const float* coef, void* xd, int B, int C, int H, int W, int Hm, int Wm, hipStream_t stream);
+int vd_sag_fold_f16(void* eps, const void* e_d, int64_t n, const float* w, hipStream_t stream);
+
 /* Token merging for self-attention (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion", 2023; the tomesd package with
  * sx = sy = 2, use_rand = False; not in the reference).  Four entry points (additive to ABI 8); none allocates or synchronises
  * (capturable).  Every one returns < 0 (vd_last_error, the text starts with the entry's name) for null pointers, an empty problem,

@@ -144,7 +144,7 @@ class CrossAttention(nn.Module, PackCache):
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
 
     def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False, repeat=1,
-                ident_from=None, tome=None):
+                ident_from=None, tome=None, sag=None):
         """ln_sums: row statistics of x for `ln` (from x's producer); out_sums: zeroed fp32 [rows, 2] the output projection
         accumulates the row statistics of ITS output into (for the LayerNorm in front of the next block part).
         defer_out: return the attention output `a` WITHOUT the output projection (the caller folds to_out + res into its next
@@ -160,8 +160,13 @@ class CrossAttention(nn.Module, PackCache):
         the tokens are an H x W grid, metric [B, N, C] is the block's un-normalised input, and the r most redundant source tokens
         are merged into their most similar destination: q | k | v as always -> ops.tome_match on the metric -> ops.tome_plan ->
         ops.tome_merge of the fused q | k | v -> ops.attention on N - r rows -> ops.tome_unmerge back to N rows -> to_out.
-        sink, when given, is called with row_of (int32 [B, N]).  It does not combine with ident_from."""
+        sink, when given, is called with row_of (int32 [B, N]).  It does not combine with ident_from.
+        sag (self-attention only; self-attention guidance): None, or a contiguous fp32 [n, N] view with n <= B: it receives the
+        column mass of the attention map of the samples [0, n) (ops.sag_mass of their q | k), whoever computed qkv.  The attention
+        itself is untouched: the output bits are those of the call without it.  It does not combine with tome."""
         c = self.inner
+        if sag is not None and not (context is None and kv is None and tome is None):
+            raise ops.VdHipError("CrossAttention(sag=...): the column mass is taken in an unmerged self-attention only")
         if tome is not None and not (context is None and kv is None):
             raise ops.VdHipError("CrossAttention(tome=...): token merging applies to self-attention only")
         if tome is not None and ident_from is not None:
@@ -183,6 +188,11 @@ class CrossAttention(nn.Module, PackCache):
                 if hip_layers.wstream_epi_level("qkv", x.numel() // x.shape[-1], x.shape[-1]):
                     kw["w_stream_epi"] = self._w_qkv_ln_stream(ln)
                 qkv = ops.linear(x, w, b, colsum=cs, ln_eps=ln.eps, ln_sums=ln_sums, **kw)
+            if sag is not None:
+                n = sag.shape[0]
+                if qkv.dim() != 3 or sag.dim() != 2 or not 0 < n <= qkv.shape[0] or sag.shape[1] != qkv.shape[1]:
+                    raise ops.VdHipError("CrossAttention(sag=...): the mass buffer %s does not fit q|k|v %s" % (tuple(sag.shape), tuple(qkv.shape)))
+                ops.sag_mass(qkv[:n, :, :c], qkv[:n, :, c:2 * c], self.heads, scale=self.scale, out=sag)
             if tome is not None:
                 tH, tW, r, metric = tome[:4]
                 if qkv.dim() != 3 or metric.dim() != 3 or metric.shape[:2] != qkv.shape[:2] or tH * tW != qkv.shape[1]:
@@ -241,7 +251,7 @@ class BasicTransformerBlock(nn.Module):
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
     def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None, ident_from=None,
-                tome=None):
+                tome=None, sag=None):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
@@ -255,7 +265,8 @@ class BasicTransformerBlock(nn.Module):
         has repeat times the samples of x.
         ident_from: handed to attn1 (CrossAttention.forward); the replicas then differ from attn1 on, so it needs repeat == 1.
         tome: None, or (H, W, r, sink) of token merging: attn1 gets (H, W, r, x, sink) -- the metric is this block's un-normalised
-        input.  With repeat > 1 the merge runs on the one replica attn1 sees."""
+        input.  With repeat > 1 the merge runs on the one replica attn1 sees.
+        sag: handed to attn1 (CrossAttention.forward): the buffer that receives the column mass of its leading samples."""
         if tome is not None:
             tome = (tome[0], tome[1], tome[2], x, tome[3] if len(tome) > 3 else None)
         if ident_from is not None and repeat > 1:
@@ -263,7 +274,7 @@ class BasicTransformerBlock(nn.Module):
         if repeat > 1 and not period_consumers(x.shape[-1], self.attn2.heads):
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d): width %d has no consumers with a batch period" % (repeat, x.shape[-1]))
         if hip_layers.LN_FOLD:  # the three LayerNorms ride in the q/k/v, q and GEGLU projections (VD_EPI_LNFOLD)
-            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome)
+            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome, sag=sag)
             C = x.shape[-1]
             fops = self.ff.chain_operands(self.norm3) if (x.is_contiguous() and ops.ff_geglu_supported(C)) else None
             if fops is not None and (ops.ff_chain_supported(C, "pre") or (post is not None and ops.ff_chain_supported(C, "post"))):
@@ -305,7 +316,7 @@ class BasicTransformerBlock(nn.Module):
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
             return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None), post=ff_post, sync=sync)
-        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome)
+        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome, sag=sag)
         x = self.attn2(self.norm2(x), context=context, res=x, kv=kv)
         x = self.ff(self.norm3(x), res=x)
         return x
@@ -337,7 +348,7 @@ class SpatialTransformer(nn.Module):
         and of the chained tail (vd.run_unet hands a guided batch over un-replicated only then)."""
         return period_consumers(self.proj_in.out_channels, self.transformer_blocks[0].attn2.heads)
 
-    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None):
+    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None, sag=None):
         """Returns alpha * (proj_out(...) + bias) + res, res defaulting to x (the block's own skip).
         alpha/res implement VD's context mixing sum_i r_i * ST_i(x) without extra passes.
         sync: callable invoked right before the ONE launch that reads `res` (the last of the block): the caller runs the blocks
@@ -348,7 +359,9 @@ class SpatialTransformer(nn.Module):
         ident_from (perturbed-attention guidance, needs repeat == 1): samples [ident_from, B) of x take the identity self-attention
         map in this block, whether q | k | v come from the chained entry kernel (width 320) or from the block's own projection.
         tome: None, or (r, sink) of token merging (r > 0): this block's self-attention merges r tokens of its H x W grid, the metric
-        being the h that enters the transformer block (at width 320 the one the chained entry kernel returns)."""
+        being the h that enters the transformer block (at width 320 the one the chained entry kernel returns).
+        sag: None, or a contiguous fp32 [n, H W] view, n <= B: the block's self-attention writes the column mass of its attention map
+        for the samples [0, n) into it (self-attention guidance); the block's output is untouched."""
         if tome is not None:
             tome = (x.shape[1], x.shape[2], int(tome[0]), tome[1] if len(tome) > 1 else None)
         assert repeat == 1 or ident_from is None, "a perturbed replica takes the replicated input"
@@ -372,7 +385,7 @@ class SpatialTransformer(nn.Module):
             if pres.is_contiguous() and self.proj_out.out_channels == inner and self.proj_out.bias is not None:
                 wp, bp = self.proj_out._w()
                 post = (wp, bp, float(alpha), pres.view(B, H * W, C), H * W)
-            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome)
+            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome, sag=sag)
             if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the block's last launch
                 out = h[0]
                 st = ops.stats_of(out)
@@ -395,7 +408,7 @@ class SpatialTransformer(nn.Module):
                 ff_post = (self.proj_out, float(alpha), pres, H * W)
         h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
                                        repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None, ident_from=ident_from,
-                                       tome=tome)
+                                       tome=tome, sag=sag)
         if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the feed-forward's output GEMM
             out = h[0]
             st = ops.stats_of(out)

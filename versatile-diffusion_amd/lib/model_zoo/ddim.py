@@ -21,7 +21,8 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import DeepCache, _freeu_arg, _pag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable, tome_blocks
+from .vd import (DeepCache, _freeu_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
+                 kv_rows, sag_map_size, sag_taps, tome_blocks)
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -214,6 +215,28 @@ def pag_weight(scale, pag_scale, guided):
     return np.float32(np.float64(pag_scale))
 
 
+def sag_weight(scale, sag_scale, guided):
+    """The fp32 weight ops.sag_fold reads (vd_sag_fold_f16, include/vd_hip.h), formed in float64 and rounded once.  Guided: the fold
+    rewrites e_u to a' = e_u + w (e_u - e_d) with w = -s_sag / (s - 1), so the update's a' + s (e_c - a') is
+    e_u + s (e_c - e_u) + s_sag (e_u - e_d).  Unguided: e_c + s_sag (e_c - e_d), w = s_sag."""
+    if guided:
+        return np.float32(-np.float64(sag_scale) / (np.float64(scale) - 1.0))
+    return np.float32(np.float64(sag_scale))
+
+
+def sag_coef_table(alphas_cumprod, timesteps):
+    """fp32 [S, 3] rows {sqrt(a_t), sqrt(1 - a_t), 1 / sqrt(a_t)} of ops.sag_degrade per DDIM index i, a_t = alphas_cumprod[timesteps[i]],
+    computed in float64: the data prediction and the re-noising of a self-attention-guidance step (diffusers' pred_x0 / add_noise)."""
+    a = np.asarray(alphas_cumprod, dtype=np.float64)[np.asarray(timesteps, dtype=np.int64)]
+    return np.stack([np.sqrt(a), np.sqrt(1.0 - a), 1.0 / np.sqrt(a)], axis=1).astype(np.float32)
+
+
+def sag_ratios(c_info_list):
+    """fp32 [T]: the normalised ratios vd.run_unet mixes the context types with (float64 r / sum r, rounded once)."""
+    r = np.array([float(ci.get("ratio", 1.0)) for ci in c_info_list], dtype=np.float64)
+    return (r / r.sum()).astype(np.float32)
+
+
 _gc_lock = threading.Lock()
 _gc_holds = [0, False]      # captures in progress in this process; whether the collector was on when the first began
 
@@ -330,6 +353,8 @@ class DDIMSampler(object):
         # x_info['tome_ratio'] / ['tome_max_downsample'] (extension keys, vd._tome_arg): None, or the TokenMerge; raises like the
         # others.  The setting travels with every forward (_eps), like FreeU's
         tome = _tome_arg(x_info, self.model, shape)
+        # x_info['sag_scale'] / ['sag_blur_sigma'] (extension keys, vd._sag_arg): None, or (s_sag, sigma); raises like the others
+        sag = _sag_arg(x_info, self.model, shape)
         # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
         c_info_list = _region_contexts(c_info_list, window, shape[0])
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
@@ -353,13 +378,14 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint, phi, interval, depth, window, pag)
+                                                 inpaint, phi, interval, depth, window, pag, sag)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
             deep = DeepCache(depth) if interval > 1 else None
             wstate = None if window is None else self._window_state(window, x, guided, pag is not None)      # once per call
             pag_step = None if pag is None else (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)),
                                                                     device=x.device, dtype=torch.float32))
+            sag_step = None if sag is None else self._sag_eager(sag, scale, guided, c_info_list, x)
             if phi > 0.:
                 intermediates["guidance_rescale"] = []
             for ci in c_info_list:
@@ -370,7 +396,7 @@ class DDIMSampler(object):
                 x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                               noise_dropout=noise_dropout, rescale=rescale,
                                               deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"),
-                                              window=wstate, pag=pag_step)
+                                              window=wstate, pag=pag_step, sag=sag_step)
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
@@ -382,6 +408,8 @@ class DDIMSampler(object):
             intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
         if pag is not None:
             intermediates["pag_layers"] = pag[1]
+        if sag is not None:
+            intermediates["sag_map"] = sag_map_size(self.model.diffuser[x_info["type"]], x.shape[2], x.shape[3])
         if tome is not None:
             th, tw = (x.shape[2], x.shape[3]) if window is None else window["key"][:2]
             intermediates["tome_tokens"] = [(H * W, H * W - r) for _, H, W, r in
@@ -489,7 +517,7 @@ class DDIMSampler(object):
                              min(m, plan["n"] - k * m), wrap, k == 0, k == nc - 1, acc=ws["acc"], out=ws["eps"])
         return ws["eps"]
 
-    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None, window=None, pag=None):
+    def _eps(self, x_info, x, t, c_info_list, guided, single, emb_rows=None, deep=None, window=None, pag=None, sag=None):
         """The UNet on latent x at timesteps t.  guided: the batch is [x; x] (ddim.py:144-149); it is handed over as (x, repeat=2)
         so the data blocks in front of the first context block run once (extension key of this package's apply_model*).
         deep: (DeepCache, "store" | "reuse") of a cached call's full / shallow step (apply_model*'s 'deep_cache').
@@ -498,15 +526,20 @@ class DDIMSampler(object):
         pag: None, or the layers of perturbed-attention guidance: one more replica, the last, runs those context blocks with
         identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward.
         x_info['tome_ratio'] / ['tome_max_downsample'] (token merging, vd._tome_arg) travel with every forward as apply_model*'s
-        'tome', so with windows the merge acts on each window's token grid."""
+        'tome', so with windows the merge acts on each window's token grid.
+        sag: None, or the fp32 [T, B, Nm] mass buffer of self-attention guidance (apply_model*'s 'sag'): the forward also writes the
+        column mass of the middle block's self-attention map of replica 0 into it."""
         if window is not None:
-            assert deep is None, "DeepCache does not combine with windows"
+            assert deep is None and sag is None, "DeepCache and sag do not combine with windows"
             return self._eps_windowed(x_info, x, t, c_info_list, guided, single, emb_rows, window, pag)
         reps = replica_count(guided, pag is not None)
         xi = {"type": x_info["type"], "x": x, "repeat": reps}
         if pag is not None:
             assert deep is None, "DeepCache does not combine with pag"
             xi["pag"] = (pag, (reps - 1) * x.shape[0])
+        if sag is not None:
+            assert deep is None, "DeepCache does not combine with sag"
+            xi["sag"] = sag
         if emb_rows is not None:
             xi["emb_rows"] = emb_rows
         if deep is not None:
@@ -520,6 +553,43 @@ class DDIMSampler(object):
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
 
+    def _sag_eager(self, sag, scale, guided, c_info_list, x):
+        """The device state of self-attention guidance for one call of the eager loop (or one p_sample_ddim*): what _new_state keeps
+        and _load_state loads on the static loop, plus "alphas", the float64 host schedule "coef" is refreshed from per step."""
+        st = self._sag_buffers(x, len(c_info_list))
+        self._sag_load(st, sag, scale, guided, c_info_list)
+        st["alphas"] = np.asarray(self.alphas_cumprod, dtype=np.float64)
+        return st
+
+    def _sag_buffers(self, x, T):
+        """The buffers of a self-attention-guidance step on the latent x [B, C, H, W] with T context types: "mass" fp32 [T, B, Nm]
+        (written by the first forward), "xd" (the degraded latent, the second forward's input), "coef" fp32 [3] = {sa, s1, isa}
+        (per step), and per call "w" fp32 [1] (sag_weight), "taps" fp32 [9] (vd.sag_taps) and "ratio" fp32 [T] (sag_ratios)."""
+        Hm, Wm = sag_map_size(self.model.diffuser["image"], x.shape[2], x.shape[3])
+        f32 = dict(device=x.device, dtype=torch.float32)
+        return {"map": (Hm, Wm), "mass": torch.zeros((T, x.shape[0], Hm * Wm), **f32), "xd": torch.empty_like(x),
+                "coef": torch.empty((3,), **f32), "w": torch.empty((1,), **f32), "taps": torch.empty((9,), **f32),
+                "ratio": torch.empty((T,), **f32)}
+
+    @staticmethod
+    def _sag_load(sg, sag, scale, guided, c_info_list):
+        """This call's fold weight, blur taps and context ratios into the buffers of _sag_buffers; sag = (s_sag, sigma)."""
+        dev = sg["w"].device
+        sg["w"].fill_(float(sag_weight(scale, sag[0], guided)))
+        sg["taps"].copy_(torch.from_numpy(sag_taps(sag[1]).astype(np.float32)).to(dev))
+        sg["ratio"].copy_(torch.from_numpy(sag_ratios(c_info_list)).to(dev))
+
+    def _sag_fold(self, sg, x_info, x, t, eps, c_info_list, single, emb_rows=None):
+        """The second half of a self-attention-guidance step, behind the first forward (which wrote sg["mass"]): ops.sag_degrade of
+        the latent x with replica 0 of eps into sg["xd"], the second forward on it -- one replica, with the replica-0 rows of the
+        contexts and of their cached K/V (vd.kv_rows: nothing is projected again), the same FreeU setting and time-embedding rows --
+        and ops.sag_fold of its prediction into replica 0 of eps (contiguous fp16 [R B, C, H, W]), in place.  t: the B timesteps."""
+        B = x.shape[0]
+        ops.sag_degrade(x, eps[:B], sg["mass"], sg["ratio"], sg["taps"], sg["coef"], sg["map"][0], sg["map"][1], out=sg["xd"])
+        c0 = [dict(ci, c=ci["c"][:B], kv_cache=kv_rows(ci.get("kv_cache"), B)) for ci in c_info_list]
+        e_d = self._eps(x_info, sg["xd"], t, c0, False, single, emb_rows)
+        return ops.sag_fold(eps, e_d.to(torch.float16).contiguous(), sg["w"])
+
     def _coef_table(self, total_steps, scale, device):
         """[S, 6] fp32 device table of {scale, 1/sqrt(a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma, sqrt(1-a_t)}; row i is
         copied into the static coef buffer before step i (a sampler on this loop returns its own [S, coef_width] table)."""
@@ -532,7 +602,7 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None, pag=False):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None, pag=False, sag=False):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
         projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
         rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
@@ -541,7 +611,9 @@ class DDIMSampler(object):
         window (the plan of _window_args): "window" holds its tables and buffers (_window_state), and "ts" has a row per
         window slot like the context batches.  pag (perturbed-attention guidance on): "ts" and the window buffers have the rows
         of replica_count(guided, pag) replicas, and "pag_w" is the fold's weight (fp32 [1], loaded per call: one graph serves
-        every positive pag_scale and every guidance scale)."""
+        every positive pag_scale and every guidance scale).  sag (self-attention guidance on): "sag" holds the buffers of
+        _sag_buffers; its weight, taps and ratios are loaded per call, its coefficients per step: one graph serves every sag_scale,
+        sigma and guidance scale."""
         nb = replica_count(guided, pag) * x.shape[0] * (1 if window is None else window["m"])
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
@@ -555,6 +627,8 @@ class DDIMSampler(object):
             st["window"] = self._window_state(window, x, guided, pag)
         if pag:
             st["pag_w"] = torch.empty((1,), device=x.device, dtype=torch.float32)
+        if sag:
+            st["sag"] = self._sag_buffers(x, len(c_info_list))
         if rescale > 0.:
             st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
                       kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
@@ -584,7 +658,10 @@ class DDIMSampler(object):
         # and perturbed-attention guidance, (on?, layers): a graph captured with it runs one more replica, the identity attention of
         # those context blocks and the fold; its scale is not in the key -- the fold's weight is loaded per call;
         # and token merging, (ratio, max_downsample) or None, in front of those two: r is an argument of the captured launches and
-        # decides the shapes behind them -- one graph per setting)
+        # decides the shapes behind them -- one graph per setting;
+        # and self-attention guidance: a further entry ("sag",) at the END when it is on, nothing when it is off (the key of a call
+        # without it is the key it always had): a graph captured with it runs the mass, the degrade, a second forward and the fold;
+        # its scale and sigma are not in the key -- weight and taps are loaded per call)
         pag = _pag_arg(x_info, self.model)
         tome = _tome_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
@@ -592,9 +669,12 @@ class DDIMSampler(object):
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
                inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"],
                None if tome is None else tome.key(), (pag is not None, None if pag is None else pag[1]), _freeu_arg(x_info))
+        if _sag_arg(x_info, self.model) is not None:
+            key = key + (("sag",),)
         return key
 
-    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False):
+    def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False,
+                      sag=False):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -605,13 +685,14 @@ class DDIMSampler(object):
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag, sag)
         self._static[key] = st                                 # most recently used last
         return st
 
-    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None):
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None, sag=None):
         """Copy this call's latent, contexts, inpainting tensors, region masks (with their inv_den; `window` is the call's
-        plan) and the weight of the perturbed-attention fold (pag_w, pag_weight) into the state and hand its context buffers and
+        plan), the weight of the perturbed-attention fold (pag_w, pag_weight) and the weight, taps and ratios of self-attention
+        guidance (sag = (s_sag, sigma, guidance scale, guided); _sag_load) into the state and hand its context buffers and
         K/V caches to c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
         st["xs"].copy_(x)
         if window is not None and "regions" in window:      # one kept graph serves every mask of the same R and geometry
@@ -621,6 +702,8 @@ class DDIMSampler(object):
             st["phi"].fill_(phi)
         if "pag_w" in st:
             st["pag_w"].fill_(float(pag_w))
+        if "sag" in st:
+            self._sag_load(st["sag"], sag[:2], sag[2], sag[3], c_info_list)
         if inpaint is not None:
             for k in ("x0", "noise", "mask"):
                 st[k].copy_(inpaint[k])
@@ -660,7 +743,7 @@ class DDIMSampler(object):
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
     def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
-                     phi=0., interval=1, depth=1, window=None, pag=None):
+                     phi=0., interval=1, depth=1, window=None, pag=None, sag=None):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry.  Returns (final fp16 latent, intermediates).
@@ -672,17 +755,24 @@ class DDIMSampler(object):
         rescale factors, the blend, the seeded noise and the solver histories see the canvas and nothing else.
         pag (None, or (s_pag, layers) of vd._pag_arg): the forward runs one more replica, perturbed, and ops.pag_fold folds its
         prediction into replica 0 between the forward and the update; the update, the rescale factors, the blend, the noise and the
-        histories see the folded pair (or single) and nothing else, so every sampler on this loop gets it."""
+        histories see the folded pair (or single) and nothing else, so every sampler on this loop gets it.
+        sag (None, or (s_sag, sigma) of vd._sag_arg): the step runs TWO forwards in sequence in the one captured graph -- the first,
+        today's, also writes the column mass of the middle block's self-attention map; ops.sag_degrade blurs and re-noises the latent
+        with it; the second forward predicts from that on one replica; ops.sag_fold folds its prediction into replica 0 (_sag_fold) --
+        and then the unchanged update, like pag's."""
         tome = _tome_arg(x_info, self.model)
         if tome is not None and tome.record is not None and self.use_graph:
             raise ValueError("tome: TokenMerge.record is an eager-only hook; this loop captures its steps into a graph (use_graph)")
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
-        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pag is not None)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None))
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pag is not None,
+                                 sag is not None)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None, sag is not None))
         replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window,
-                                        None if pag is None else pag_weight(scale, pag[0], guided))
+                                        None if pag is None else pag_weight(scale, pag[0], guided),
+                                        None if sag is None else (sag[0], sag[1], scale, guided))
+        sag_tab = None if sag is None else torch.from_numpy(sag_coef_table(self.alphas_cumprod, timesteps[:total_steps])).to(x.device)
         reps = replica_count(guided, pag is not None)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
@@ -691,10 +781,13 @@ class DDIMSampler(object):
 
         def body(mode=None):
             eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows,
-                            None if mode is None else (st["deep"], mode), st.get("window"), None if pag is None else pag[1])
+                            None if mode is None else (st["deep"], mode), st.get("window"), None if pag is None else pag[1],
+                            None if sag is None else st["sag"]["mass"])
             eps = eps.contiguous()
             if pag is not None:
                 eps = ops.pag_fold(eps, reps, st["pag_w"])      # the folded pair (single): what every update below reads
+            if sag is not None:     # degrade, second forward, fold into replica 0: what every update below reads
+                eps = self._sag_fold(st["sag"], x_info, st["xs"], st["ts"][:st["xs"].shape[0]], eps, c_info_list, single, emb_rows)
             self._update_static(st, eps, guided)
 
         bodies = {"graph": body if interval == 1 else (lambda: body("store")), "graph_shallow": lambda: body("reuse")}
@@ -714,6 +807,8 @@ class DDIMSampler(object):
             index = total_steps - i - 1
             st["ts"].copy_(steps_dev[i].expand(st["ts"].shape[0]))       # device-side refresh, no host sync
             st["coef"].copy_(table[index])
+            if sag_tab is not None:
+                st["sag"]["coef"].copy_(sag_tab[index])
             if rng_tab is not None:
                 st["rng"].copy_(rng_tab[i])
             if inpaint is not None:
@@ -795,14 +890,16 @@ class DDIMSampler(object):
             return None
 
     def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None,
-              deep=None, window=None, pag=None):
+              deep=None, window=None, pag=None, sag=None):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
         the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep, window: _eps's.
-        pag: None, or (layers, the fold's weight as a device fp32 [1]) of perturbed-attention guidance."""
+        pag: None, or (layers, the fold's weight as a device fp32 [1]) of perturbed-attention guidance.
+        sag: None, or the state of _sag_eager: the step of self-attention guidance (_sag_fold) between the forward and the update."""
         reps = replica_count(guided, pag is not None)
         rows = reps * x.shape[0] * (1 if window is None else window["plan"]["m"])
         t_in = torch.full((rows,), step, device=x.device, dtype=torch.long)
-        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep, window=window, pag=None if pag is None else pag[0])
+        eps = self._eps(x_info, x, t_in, c_info_list, guided, single, deep=deep, window=window, pag=None if pag is None else pag[0],
+                        sag=None if sag is None else sag["mass"])
         sigma = float(self.ddim_sigmas[index])
         # drawn on every step like the reference's noise_like(x) (ddim.py:167 there): same generator consumption, and for
         # eta > 0 the same noise values as a reference running in fp16 on this device
@@ -821,6 +918,10 @@ class DDIMSampler(object):
         eps = eps.contiguous()
         if pag is not None:
             eps = ops.pag_fold(eps, reps, pag[1])
+        if sag is not None:
+            a = sag["alphas"][step]
+            sag["coef"].copy_(torch.tensor([np.sqrt(a), np.sqrt(1.0 - a), 1.0 / np.sqrt(a)], dtype=torch.float32))
+            eps = self._sag_fold(sag, x_info, x, t_in[:x.shape[0]], eps.to(torch.float16), c_info_list, single)
         if rescale is None:
             return ops.cfg_ddim_step(x, eps, **scalars) + (None,)
         kfac = ops.cfg_rescale_factor(eps, rescale[0], rescale[1], x.numel() // x.shape[0])
@@ -856,12 +957,15 @@ class DDIMSampler(object):
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         pag = _pag_arg(x_info, self.model)      # so is perturbed-attention guidance: one more replica and the fold
         _tome_arg(x_info, self.model, x_info["x"].shape)    # and token merging: the step's forward applies it (_eps)
+        sag = _sag_arg(x_info, self.model, x_info["x"].shape)   # and self-attention guidance: the step runs its second forward
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list, pag=pag is not None)
         x = x_info["x"]
         if pag is not None:
             pag = (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)), device=x.device, dtype=torch.float32))
-        xp, p0, _ = self._step(x.to(torch.float16).contiguous(), x_info, cis, int(t[0]), index, guided, scale,
+        x16 = x.to(torch.float16).contiguous()
+        xp, p0, _ = self._step(x16, x_info, cis, int(t[0]), index, guided, scale,
                                temperature, single, noise_dropout=noise_dropout,
-                               rescale=self._rescale_scalars(scale, phi, x.device), pag=pag)
+                               rescale=self._rescale_scalars(scale, phi, x.device), pag=pag,
+                               sag=None if sag is None else self._sag_eager(sag, scale, guided, cis, x16))
         return xp.to(x.dtype), p0.to(x.dtype)

@@ -98,7 +98,7 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
                       window_weight="uniform", window_batch=8, freeu=None, region_masks=None, pag_scale=None,
                       pag_layers=None, tome_ratio=None, tome_max_downsample=None, vae_tile=None, vae_tile_stride=None,
-                      vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None):
+                      vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None, sag_scale=None, sag_blur_sigma=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -125,6 +125,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     pag_scale, pag_layers: the samplers' x_info['pag_scale'] and x_info['pag_layers'] (perturbed-attention guidance, vd._pag_arg;
     None = the key is not set).  The perturbed replica is per sample, so a rank's slice sees what the whole batch would.
+
+    sag_scale, sag_blur_sigma: the samplers' x_info['sag_scale'] and x_info['sag_blur_sigma'] (self-attention guidance, vd._sag_arg;
+    None = the key is not set).  The attention map, the mask and the second forward are per sample, so a rank's slice sees what the
+    whole batch would.
 
     tome_ratio, tome_max_downsample: the samplers' x_info['tome_ratio'] and x_info['tome_max_downsample'] (token merging,
     vd._tome_arg; None = the key is not set).  The merge is per sample, so a rank's slice sees what the whole batch would.
@@ -179,6 +183,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             x_info["pag_scale"] = pag_scale
         if pag_layers is not None:
             x_info["pag_layers"] = pag_layers
+        if sag_scale is not None:
+            x_info["sag_scale"] = sag_scale
+        if sag_blur_sigma is not None:
+            x_info["sag_blur_sigma"] = sag_blur_sigma
         if tome_ratio is not None:
             x_info["tome_ratio"] = tome_ratio
         if tome_max_downsample is not None:

@@ -513,8 +513,123 @@ def _tome_fwd_arg(x_info):
     return tm
 
 
+# ---- self-attention guidance (x_info['sag_scale'], x_info['sag_blur_sigma']; forward key x_info['sag']) ------------------------
+# Hong et al., "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance" (ICCV 2023); diffusers'
+# StableDiffusionSAGPipeline(sag_scale).  A forward with x_info['sag'] also writes the column mass of the middle context block's
+# self-attention map of replica 0 (ops.sag_mass); the samplers degrade the latent with it (ops.sag_degrade), predict a second time
+# and fold that prediction into the step's eps (ops.sag_fold; contracts in include/vd_hip.h).
+SAG_MAX_TOKENS = 1024
+
+
+def sag_map_size(net, H, W):
+    """(Hm, Wm): the token grid of the middle stage's first context block of the 2-D data net `net` on an H x W latent -- the block
+    pag_layers names "mid"; every Downsample in front of it halves a side, rounding up.  ValueError (matching 'sag') for a net
+    without such a walk."""
+    from .openaimodel import Downsample, UNetModel0D_Next, Upsample
+    if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("i_order", "m_order", "o_order", "data_blocks")):
+        raise ValueError("sag needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+    if "c" not in list(net.m_order):
+        raise ValueError("sag: the middle stage of %s has no context block" % type(net).__name__)
+    d_iter = iter(net.data_blocks)
+    Hm, Wm = int(H), int(W)
+    for i, s in enumerate(list(net.i_order) + list(net.m_order)):
+        if s == "d":
+            blk = next(d_iter)
+            if any(isinstance(m, Downsample) for m in blk.modules()):
+                Hm, Wm = (Hm + 1) // 2, (Wm + 1) // 2
+            elif any(isinstance(m, Upsample) for m in blk.modules()):
+                Hm, Wm = Hm * 2, Wm * 2
+        elif s == "c" and i >= len(net.i_order):
+            break
+    return Hm, Wm
+
+
+def sag_taps(sigma):
+    """float64 [9]: g[k] = exp(-((k - 4) / sigma)^2 / 2) / sum, the normalised Gaussian of diffusers' gaussian_blur_2d at kernel
+    size 9."""
+    g = np.exp(-0.5 * ((np.arange(9, dtype=np.float64) - 4.0) / float(sigma)) ** 2)
+    return g / g.sum()
+
+
+def _sag_real(value):
+    return not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, float, np.integer, np.floating)) and np.isfinite(float(value))
+
+
+def _sag_arg(x_info, model, shape=None):
+    """The sampler keys of self-attention guidance validated: None when x_info['sag_scale'] is absent, None or 0 (off: today's call,
+    'sag_blur_sigma' is then ignored), else (s_sag, sigma) as floats, sigma = x_info['sag_blur_sigma'] (default 1.0) on the 2-D
+    image flow.  ValueError (matching 'sag') for a scale that is no real number, negative or not finite, a sigma that is no finite
+    real number > 0, another flow, with `shape` ([B, C, H, W]) a latent side below 5 (the reflected 9-tap blur) or a middle token
+    grid of more than 1024 tokens, and for the combinations left out of scope on purpose: window / region_masks, cache_interval > 1,
+    pag_scale and tome_ratio.  Touches no device."""
+    value = x_info.get("sag_scale")
+    if value is None:
+        return None
+    if not _sag_real(value) or float(value) < 0.:
+        raise ValueError("x_info['sag_scale'] must be a finite real number >= 0, got %r" % (value,))
+    if float(value) == 0.:
+        return None
+    sigma = x_info.get("sag_blur_sigma", 1.0)
+    if not _sag_real(sigma) or not float(sigma) > 0.:
+        raise ValueError("x_info['sag_blur_sigma'] (sag) must be a finite real number > 0, got %r" % (sigma,))
+    if x_info.get("type") != "image":
+        raise ValueError("sag_scale applies to x_info['type'] == 'image' only (the self-attention map of the 2-D net), got %r"
+                         % (x_info.get("type"),))
+    if x_info.get("window") is not None or x_info.get("region_masks") is not None:
+        raise ValueError("sag_scale with window / region_masks is out of scope on purpose: one attention map per window")
+    cache = x_info.get("cache_interval", 1)
+    if not isinstance(cache, (bool, str)) and isinstance(cache, (int, np.integer)) and cache > 1:
+        raise ValueError("sag_scale with cache_interval > 1 is out of scope on purpose: DeepCache and sag do not combine")
+    if x_info.get("pag_scale") not in (None, 0, 0.) or x_info.get("pag") is not None:
+        raise ValueError("sag_scale with pag_scale is out of scope on purpose: one replica-0 fold per step")
+    if x_info.get("tome_ratio") not in (None, 0, 0.) or x_info.get("tome") is not None:
+        raise ValueError("sag_scale with tome_ratio is out of scope on purpose: the mass is taken on the unmerged token grid")
+    net = model.diffuser[x_info["type"]]
+    if shape is not None:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 4:
+            raise ValueError("sag: the latent shape must be [B, C, H, W], got %s" % (shape,))
+        if shape[2] < 5 or shape[3] < 5:
+            raise ValueError("sag: the latent is %d x %d, the reflected 9-tap blur needs H, W >= 5" % shape[2:])
+        Hm, Wm = sag_map_size(net, shape[2], shape[3])
+        if Hm * Wm > SAG_MAX_TOKENS:
+            raise ValueError("sag: the middle block has %d x %d tokens, at most %d" % (Hm, Wm, SAG_MAX_TOKENS))
+    else:
+        sag_map_size(net, 8, 8)
+    return float(value), float(sigma)
+
+
+def _sag_fwd_arg(x_info, contexts):
+    """x_info['sag'] (extension key of apply_model*, set by the samplers) validated: None, or the caller-owned fp32 [T, B, Nm] device
+    tensor -- T the number of context types of the call, B the samples of ONE replica, Nm the tokens of the middle context block."""
+    buf = x_info.get("sag")
+    if buf is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("sag applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if not (torch.is_tensor(buf) and buf.dtype == torch.float32 and buf.dim() == 3 and buf.is_contiguous()
+            and buf.shape[0] == contexts and buf.shape[1] == x_info["x"].shape[0]):
+        raise ValueError("x_info['sag'] must be a contiguous fp32 [%d, %d, Nm] tensor, got %r"
+                         % (contexts, x_info["x"].shape[0], tuple(buf.shape) if torch.is_tensor(buf) else buf))
+    if buf.device != x_info["x"].device:
+        raise ValueError("x_info['sag'] lives on %s, the latent on %s" % (buf.device, x_info["x"].device))
+    return buf
+
+
+def kv_rows(cache, rows):
+    """A context K/V cache for forwards on the first `rows` samples of the batch `cache` was filled for: the same entries as
+    batch-slice views, projected by the forward that filled `cache` (nothing is projected again).  None without a cache; an entry
+    still marked stale is left out (it would be projected from the sliced context on use)."""
+    if cache is None:
+        return None
+    stale = cache.get(_KV_STALE, ())
+    out = {mid: kv[:rows] for mid, kv in cache.items() if not isinstance(mid, str) and mid not in stale}
+    out[_KV_MODULES] = {mid: m for mid, m in cache.get(_KV_MODULES, {}).items() if mid in out}
+    return out
+
+
 def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None,
-             tome=None):
+             tome=None, sag=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -541,7 +656,25 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     not combine with deep (ValueError).
     tome: None, or a TokenMerge with ratio > 0: the context blocks of tome_blocks (every context type's block at those walk
     indices) merge r tokens in their self-attention (SpatialTransformer.forward(tome=(r, sink))); with its `record` set every such
-    block appends (walk index, row_of.clone()) -- not under graph capture (ValueError).  It does not combine with pag (ValueError)."""
+    block appends (walk index, row_of.clone()) -- not under graph capture (ValueError).  It does not combine with pag (ValueError).
+    sag: None, or the fp32 [T, B, Nm] buffer of _sag_fwd_arg (T context types, B = x.shape[0], the rows of one replica): the middle
+    stage's first context block (sag_map_size's; pag_layers' "mid") writes the column mass of its self-attention map, ops.sag_mass,
+    for the rows [0, B) of the batch -- replica 0 -- type t's module into sag[t], on the stream that module runs on (the joins of the
+    forked branches order the writes before the next launch on the caller's stream); a half-batch branch holding samples [b0, b1)
+    writes the rows [b0, min(b1, B)).  Nothing else changes: the eps bits are those of the forward without it.  It does not combine
+    with tome or deep (ValueError)."""
+    smap = None
+    if sag is not None:
+        if x.dim() != 4:
+            raise ValueError("sag needs a 2-D data net (x_info['type'] == 'image')")
+        if tome is not None or deep is not None:
+            raise ValueError("sag does not combine with tome or deep_cache")
+        if mixing_type != "attention":
+            raise ValueError("sag needs mixing_type 'attention' (one mass per context type)")
+        Hm, Wm = sag_map_size(data_net, x.shape[-2], x.shape[-1])
+        if sag.shape[0] != len(ctx_specs) or sag.shape[1] != x.shape[0] or sag.shape[2] != Hm * Wm:
+            raise ValueError("sag: the mass buffer %s is not [%d, %d, %d x %d]" % (tuple(sag.shape), len(ctx_specs), x.shape[0], Hm, Wm))
+        smap = (pag_context_blocks(data_net)[1], sag)
     tmap = None
     if tome is not None:
         if x.dim() != 4:
@@ -603,18 +736,25 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None):
+    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None, sag=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
         repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them.
         ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag).
-        tome: None, or (r, sink) of token merging for these blocks' self-attention."""
+        tome: None, or (r, sink) of token merging for these blocks' self-attention.
+        sag: None, or the mass buffer [T, B, Nm] of self-attention guidance: module t writes the rows of replica 0 that h holds."""
         single = len(modules) == 1
         pkw = {} if ident_from is None else {"ident_from": int(ident_from)}
         if tome is not None:
             pkw["tome"] = tome
+        skw = [{} for _ in modules]
+        if sag is not None:
+            lo, hi = (0, sag.shape[1]) if sl is None else (sl[0], min(sl[1], sag.shape[1]))
+            if hi > lo:
+                skw = [{"sag": sag[t, lo:hi]} for t in range(len(modules))]
         if repeat > 1:
             assert single and sl is None and ident_from is None
-            return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat, **pkw)
+            return modules[0](h, None, specs[0][1], kv=context_kv(modules[0], specs[0]), alpha=1.0, res=None, repeat=repeat, **pkw,
+                              **skw[0])
         kvs = [context_kv(m, sp) for m, sp in zip(modules, specs)]
         if sl is not None:
             kvs = [None if kv is None else kv[sl[0]:sl[1]] for kv in kvs]
@@ -625,8 +765,8 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
         # the multi-context workloads one type's launches fill half the chip.  Only the last launches are ordered, by events.
         if single or not CTX_FORK or not h.is_cuda:
             out = None
-            for module, spec, kv, r in zip(modules, specs, kvs, rs):
-                out = module(h, None, spec[1], kv=kv, alpha=1.0 if single else float(r), res=out, **pkw)
+            for module, spec, kv, r, sk in zip(modules, specs, kvs, rs, skw):
+                out = module(h, None, spec[1], kv=kv, alpha=1.0 if single else float(r), res=out, **pkw, **sk)
             return out
         main = torch.cuda.current_stream()
         sides = _side_streams(h.device, len(modules) - 1)
@@ -639,7 +779,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
             with torch.cuda.stream(st):
                 tok = order.enter(st, first=i == 0)
                 out = module(h, None, spec[1], kv=kv, alpha=float(r), res=prev,
-                             sync=(None if prev_done is None else (lambda e=prev_done, s_=st: s_.wait_event(e))), **pkw)
+                             sync=(None if prev_done is None else (lambda e=prev_done, s_=st: s_.wait_event(e))), **pkw, **skw[i])
                 ev = torch.cuda.Event()
                 ev.record(st)
                 order.leave(st, tok)
@@ -663,12 +803,16 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     # remembers only how many rows the previous forward took)
     # (a shallow forward takes less than a full one and the two alternate: one remembered value per kind of forward)
     need_key = "_vd_rowsum_need" if deep is None or deep[1] == "store" else "_vd_rowsum_need_reuse%d" % deep[0].depth
+    # (so do the two forwards of a self-attention-guidance step, all replicas and one: the batch the net saw first keeps the plain
+    # key, any other number of rows remembers its own value)
+    if repeat * nb != data_net.__dict__.setdefault("_vd_rowsum_rows", repeat * nb):
+        need_key += "_rows%d" % (repeat * nb)
     arena = ops.RowSumArena(data_net.__dict__.get(need_key, 0))
     arena.begin(x.device)
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
                               h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
-                              fmap or None, pag, tmap)
+                              fmap or None, pag, tmap, smap)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -709,8 +853,8 @@ def _fork_region(steps, hw0, thr):
 
 
 def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None,
-                   pag=None, tome=None):
-    """deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
+                   pag=None, tome=None, sag=None):
+    """sag: None, or (walk index of the middle stage's first context block, the mass buffer) of run_unet.  deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
     the active FreeU stages.  pag: None, or (layers, row0) of run_unet.  tome: None, or ({walk index of a merging context block: r},
     the TokenMerge's record list or None)."""
     state = {"shared": shared}
@@ -745,6 +889,8 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 elif tome is not None and st[4] in tome[0]:
                     sink = None if tome[1] is None else (lambda row_of, ci=st[4], rec=tome[1]: rec.append((ci, row_of.clone())))
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, tome=(tome[0][st[4]], sink))
+                elif sag is not None and st[4] == sag[0]:
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, sag=sag[1])
                 else:
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
             elif st[0] == "save":
@@ -977,10 +1123,11 @@ class VD_v2_0(nn.Module):
         freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])   # extension key: (layers, row0), see run_unet
         tome = _tome_fwd_arg(x_info)    # extension key: a TokenMerge, see run_unet
+        sag = _sag_fwd_arg(x_info, 1)   # extension key: the fp32 [1, B, Nm] mass buffer of self-attention guidance, see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome).to(x.dtype)
+                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome, sag=sag).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -992,10 +1139,11 @@ class VD_v2_0(nn.Module):
         freeu = _freeu_arg(x_info)
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])
         tome = _tome_fwd_arg(x_info)
+        sag = _sag_fwd_arg(x_info, len(c_info_list))
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
         specs = [(self.diffuser[ci["type"]].context_blocks, self._prep(ci["c"]), ci["ratio"], ci.get("kv_cache"))
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
                         repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag,
-                        tome=tome).to(x.dtype)
+                        tome=tome, sag=sag).to(x.dtype)

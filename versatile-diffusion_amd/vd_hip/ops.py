@@ -1508,6 +1508,88 @@ def pag_fold(eps, reps, w):
     return eps[:(reps - 1) * (eps.shape[0] // reps)]
 
 
+SAG_MAX_TOKENS = 1024      # vd_sag_mass_f16 keeps the row statistics of one head in LDS
+
+
+def sag_mass(q, k, heads, *, scale=None, out=None):
+    """The column mass of a self-attention map (vd_sag_mass_f16, contract in include/vd_hip.h): q, k [B, N, heads * D] fp16 views
+    with unit inner stride (column slices of a fused projection and batch slices included) -> fp32 [B, N]:
+    mass[b, j] = (1 / heads) sum_h sum_i softmax_j(scale q_i . k_j), in fp32 throughout.  out: a contiguous fp32 [B, N] view to
+    write into.  One launch, bit-identical run to run."""
+    _tome_rows(q, "q"); _tome_rows(k, "k")
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise VdHipError("sag_mass: heads must be a positive int, got %r" % (heads,))
+    B, N, C = q.shape
+    if tuple(k.shape) != (B, N, C) or C % heads or B < 1 or N < 1:
+        raise VdHipError("sag_mass: q %s and k %s must be the same [B, N, heads * D]" % (tuple(q.shape), tuple(k.shape)))
+    if N > SAG_MAX_TOKENS:
+        raise VdHipError("sag_mass: N = %d tokens, at most %d" % (N, SAG_MAX_TOKENS))
+    D = C // heads
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    else:
+        _req(out, "out", torch.float32)
+        if tuple(out.shape) != (B, N):
+            raise VdHipError("sag_mass: out %s is not [%d, %d]" % (tuple(out.shape), B, N))
+    if scale is None:
+        scale = D ** -0.5
+    with _Timed("sag_mass_kernel<%d>" % D, 4.0 * B * N * N * C, 4.0 * B * N * C + 4.0 * B * N):
+        _check(lib().vd_sag_mass_f16(_ptr(q), _ptr(k), _ptr(out), B, heads, N, D, q.stride(1), k.stride(1), q.stride(0), k.stride(0),
+                                     float(scale), _stream()))
+    return out
+
+
+def sag_degrade(x, eps0, mass, ratio, taps, coef, Hm, Wm, out=None):
+    """The degraded latent of a self-attention-guidance step (vd_sag_degrade_f16, contract in include/vd_hip.h): x, eps0 fp16
+    [B, C, H, W]; mass fp32 [T, B, Hm Wm]; ratio fp32 [T]; taps fp32 [9]; coef fp32 [3] = {sa, s1, isa}, all on the device ->
+    fp16 [B, C, H, W]: where the ratio-combined mass of a pixel's token exceeds 1 the data prediction is blurred, then everything is
+    re-noised with eps0.  One launch.  ValueError for H or W below 5."""
+    _req(x, "x"); _req(eps0, "eps0")
+    for t, n in ((mass, "mass"), (ratio, "ratio"), (taps, "taps"), (coef, "coef")):
+        _req(t, n, torch.float32)
+    if x.dim() != 4 or tuple(eps0.shape) != tuple(x.shape) or x.numel() == 0:
+        raise VdHipError("sag_degrade: x %s and eps0 %s must be the same [B, C, H, W]" % (tuple(x.shape), tuple(eps0.shape)))
+    B, C, H, W = x.shape
+    if H < 5 or W < 5:
+        raise ValueError("sag_degrade: the plane is %d x %d, the reflected 9-tap blur needs H, W >= 5" % (H, W))
+    for v in (Hm, Wm):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise VdHipError("sag_degrade: the map size must be positive ints, got %r x %r" % (Hm, Wm))
+    if mass.dim() != 3 or mass.shape[0] < 1 or tuple(mass.shape[1:]) != (B, Hm * Wm):
+        raise VdHipError("sag_degrade: mass %s is not [T, %d, %d x %d]" % (tuple(mass.shape), B, Hm, Wm))
+    T = mass.shape[0]
+    if ratio.numel() != T or taps.numel() != 9 or coef.numel() != 3:
+        raise VdHipError("sag_degrade: ratio %s / taps %s / coef %s are not [%d] / [9] / [3]"
+                         % (tuple(ratio.shape), tuple(taps.shape), tuple(coef.shape), T))
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _req(out, "out")
+        if tuple(out.shape) != tuple(x.shape):
+            raise VdHipError("sag_degrade: out %s is not %s" % (tuple(out.shape), tuple(x.shape)))
+        if out.data_ptr() in (x.data_ptr(), eps0.data_ptr()):
+            raise VdHipError("sag_degrade: out must not alias x or eps0 (a tile reads its neighbours' pixels)")
+    with _Timed("sag_degrade_kernel", 40.0 * x.numel(), 6.0 * x.numel()):
+        _check(lib().vd_sag_degrade_f16(_ptr(x), _ptr(eps0), _ptr(mass), _ptr(ratio), T, _ptr(taps), _ptr(coef), _ptr(out), B, C, H, W,
+                                        Hm, Wm, _stream()))
+    return out
+
+
+def sag_fold(eps, e_d, w):
+    """Fold the degraded prediction of a self-attention-guidance step into replica 0 (vd_sag_fold_f16, contract in include/vd_hip.h):
+    eps fp16 [R B, ...] contiguous, e_d fp16 [B, ...] contiguous, w a device fp32 [1] (-s_sag / (s - 1), or s_sag).  In place on
+    eps[:B], one launch.  Returns eps."""
+    _req(eps, "eps"); _req(e_d, "e_d"); _req(w, "w", torch.float32)
+    n = e_d.numel()
+    if n == 0 or eps.dim() < 1 or e_d.dim() != eps.dim() or eps.shape[0] % e_d.shape[0] or tuple(eps.shape[1:]) != tuple(e_d.shape[1:]):
+        raise VdHipError("sag_fold: eps %s does not hold whole replicas of e_d %s" % (tuple(eps.shape), tuple(e_d.shape)))
+    if w.numel() < 1:
+        raise VdHipError("sag_fold: w must hold one element")
+    with _Timed("sag_fold_kernel", 2.0 * n, 6.0 * n):
+        _check(lib().vd_sag_fold_f16(_ptr(eps), _ptr(e_d), n, _ptr(w), _stream()))
+    return eps
+
+
 TOME_WIDTHS = (32, 64, 128, 320, 640)      # the metric widths vd_tome_match_f16 has an instance for
 
 
