@@ -811,6 +811,29 @@ int vd_tome_merge_f16(const void* x, int ldx, int64_t sx, int cols, const int* r
 int vd_tome_unmerge_f16(const void* a, int lda, int64_t sa, int cols, const int* row_of, int B, int H, int W, int r, void* out,
                         int ldo, int64_t so, hipStream_t stream);
 
+/* HyperTile: tiled self-attention (tfernd, "HyperTile: Tiled-optimizations for Stable-Diffusion", 2023; not in the reference).  Two
+ * entry points (additive to ABI 8); neither allocates or synchronises (capturable), each is ONE launch whatever B is, and both are
+ * bit-exact copies of 16-byte chunks: a fixed, data-independent permutation of rows.
+ *
+ * The tokens of a sample are n = y * W + x on its H x W grid, cut into nty x ntx tiles of th x tw tokens (nty = H / th,
+ * ntx = W / tw).  The tiled tensor t is CONTIGUOUS fp16 [B nty ntx, th tw, cols]: a tile is a sample of its own, so an attention
+ * over t attends inside a tile only.
+ *
+ * vd_tile_tokens_f16: x fp16 [B, H W, cols], row n of sample b at x + b * sx + n * ldx (elements; cols a multiple of 8 and rows
+ * 16-byte aligned, so the fused q | k | v of a block, a column slice of it and a batch slice qualify as they are) ->
+ *     out[(b * nty + ty) * ntx + tx, i * tw + j, :] = x[b, (ty * th + i) * W + tx * tw + j, :]      0 <= i < th, 0 <= j < tw
+ * vd_untile_tokens_f16: the exact inverse, a [B nty ntx, th tw, cols] contiguous -> out [B, H W, cols] (ldo, so): every row of out
+ * is written exactly once.  One tile (th = H, tw = W) is the identity copy.
+ *
+ * Both return < 0 (vd_last_error, the text starts with the entry's name) and launch nothing for a null pointer, a non-positive
+ * size, cols % 8 != 0, H % th != 0 or W % tw != 0, a leading dimension below cols, a pointer that is not 16-byte aligned, a leading
+ * dimension or sample stride that is no multiple of 8, a sample stride (B > 1) below the rows of a sample, and B H W cols / 8 >= 2^32
+ * (the chunk index is 32-bit; every offset is 64-bit). */
+int vd_tile_tokens_f16(const void* x, int ldx, int64_t sx, int cols, int B, int H, int W, int th, int tw, void* out,
+                       hipStream_t stream);
+int vd_untile_tokens_f16(const void* a, int cols, int B, int H, int W, int th, int tw, void* out, int ldo, int64_t so,
+                         hipStream_t stream);
+
 /* q_sample: out = sa[b] * x0 + sb[b] * noise  (lib/model_zoo/vd.py:221-224). */
 int vd_q_sample_f16(const void* x0, const void* noise, const float* sa, const float* sb, void* out, int B,
                     int64_t per_batch, hipStream_t stream);

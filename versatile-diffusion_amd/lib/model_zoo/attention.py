@@ -144,7 +144,7 @@ class CrossAttention(nn.Module, PackCache):
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
 
     def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False, repeat=1,
-                ident_from=None, tome=None, sag=None):
+                ident_from=None, tome=None, sag=None, tile=None):
         """ln_sums: row statistics of x for `ln` (from x's producer); out_sums: zeroed fp32 [rows, 2] the output projection
         accumulates the row statistics of ITS output into (for the LayerNorm in front of the next block part).
         defer_out: return the attention output `a` WITHOUT the output projection (the caller folds to_out + res into its next
@@ -163,8 +163,17 @@ class CrossAttention(nn.Module, PackCache):
         sink, when given, is called with row_of (int32 [B, N]).  It does not combine with ident_from.
         sag (self-attention only; self-attention guidance): None, or a contiguous fp32 [n, N] view with n <= B: it receives the
         column mass of the attention map of the samples [0, n) (ops.sag_mass of their q | k), whoever computed qkv.  The attention
-        itself is untouched: the output bits are those of the call without it.  It does not combine with tome."""
+        itself is untouched: the output bits are those of the call without it.  It does not combine with tome.
+        tile (self-attention only; HyperTile, contract in include/vd_hip.h): None, or (H, W, th, tw) -- the tokens are an H x W grid
+        cut into th x tw tiles and every tile attends inside itself: q | k | v as always, whoever computed it -> ops.tile_tokens of
+        the fused tensor -> ops.attention on its [B nt, th tw, *] slices (nt = (H / th) (W / tw)) -> ops.untile_tokens -> to_out.
+        It does not combine with tome or sag.  With ident_from the identity rows are per token and commute with the permutation:
+        the tiled batch takes ident_from * nt, so the perturbed samples are v, bit for bit, as without tiles."""
         c = self.inner
+        if tile is not None and not (context is None and kv is None):
+            raise ops.VdHipError("CrossAttention(tile=...): tiled attention applies to self-attention only")
+        if tile is not None and (tome is not None or sag is not None):
+            raise ops.VdHipError("CrossAttention(tile=...): tiled attention does not combine with tome or sag")
         if sag is not None and not (context is None and kv is None and tome is None):
             raise ops.VdHipError("CrossAttention(sag=...): the column mass is taken in an unmerged self-attention only")
         if tome is not None and not (context is None and kv is None):
@@ -193,7 +202,17 @@ class CrossAttention(nn.Module, PackCache):
                 if qkv.dim() != 3 or sag.dim() != 2 or not 0 < n <= qkv.shape[0] or sag.shape[1] != qkv.shape[1]:
                     raise ops.VdHipError("CrossAttention(sag=...): the mass buffer %s does not fit q|k|v %s" % (tuple(sag.shape), tuple(qkv.shape)))
                 ops.sag_mass(qkv[:n, :, :c], qkv[:n, :, c:2 * c], self.heads, scale=self.scale, out=sag)
-            if tome is not None:
+            if tile is not None:
+                tH, tW, th, tw = (int(v) for v in tile)
+                if qkv.dim() != 3 or tH * tW != qkv.shape[1] or th <= 0 or tw <= 0 or tH % th or tW % tw:
+                    raise ops.VdHipError("CrossAttention(tile=%r): q|k|v %s is not [B, %d x %d, *] in whole tiles"
+                                         % (tuple(tile), tuple(qkv.shape), tH, tW))
+                nt = (tH // th) * (tW // tw)
+                m = ops.tile_tokens(qkv, tH, tW, th, tw)
+                ikw = {} if ident_from is None else {"ident_from": int(ident_from) * nt}
+                a = ops.attention(m[..., :c], m[..., c:2 * c], m[..., 2 * c:], self.heads, scale=self.scale, **ikw)
+                a = ops.untile_tokens(a, qkv.shape[0], tH, tW, th, tw)
+            elif tome is not None:
                 tH, tW, r, metric = tome[:4]
                 if qkv.dim() != 3 or metric.dim() != 3 or metric.shape[:2] != qkv.shape[:2] or tH * tW != qkv.shape[1]:
                     raise ops.VdHipError("CrossAttention(tome=...): the metric %s / q|k|v %s are not [B, %d x %d, *]"
@@ -251,7 +270,7 @@ class BasicTransformerBlock(nn.Module):
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
     def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None, ident_from=None,
-                tome=None, sag=None):
+                tome=None, sag=None, tile=None):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
@@ -266,7 +285,9 @@ class BasicTransformerBlock(nn.Module):
         ident_from: handed to attn1 (CrossAttention.forward); the replicas then differ from attn1 on, so it needs repeat == 1.
         tome: None, or (H, W, r, sink) of token merging: attn1 gets (H, W, r, x, sink) -- the metric is this block's un-normalised
         input.  With repeat > 1 the merge runs on the one replica attn1 sees.
-        sag: handed to attn1 (CrossAttention.forward): the buffer that receives the column mass of its leading samples."""
+        sag: handed to attn1 (CrossAttention.forward): the buffer that receives the column mass of its leading samples.
+        tile: handed to attn1 (CrossAttention.forward): (H, W, th, tw) of HyperTile.  With repeat > 1 the tiled attention runs on
+        the one replica attn1 sees."""
         if tome is not None:
             tome = (tome[0], tome[1], tome[2], x, tome[3] if len(tome) > 3 else None)
         if ident_from is not None and repeat > 1:
@@ -274,7 +295,7 @@ class BasicTransformerBlock(nn.Module):
         if repeat > 1 and not period_consumers(x.shape[-1], self.attn2.heads):
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d): width %d has no consumers with a batch period" % (repeat, x.shape[-1]))
         if hip_layers.LN_FOLD:  # the three LayerNorms ride in the q/k/v, q and GEGLU projections (VD_EPI_LNFOLD)
-            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome, sag=sag)
+            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome, sag=sag, tile=tile)
             C = x.shape[-1]
             fops = self.ff.chain_operands(self.norm3) if (x.is_contiguous() and ops.ff_geglu_supported(C)) else None
             if fops is not None and (ops.ff_chain_supported(C, "pre") or (post is not None and ops.ff_chain_supported(C, "post"))):
@@ -316,7 +337,7 @@ class BasicTransformerBlock(nn.Module):
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
             return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None), post=ff_post, sync=sync)
-        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome, sag=sag)
+        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome, sag=sag, tile=tile)
         x = self.attn2(self.norm2(x), context=context, res=x, kv=kv)
         x = self.ff(self.norm3(x), res=x)
         return x
@@ -348,7 +369,7 @@ class SpatialTransformer(nn.Module):
         and of the chained tail (vd.run_unet hands a guided batch over un-replicated only then)."""
         return period_consumers(self.proj_in.out_channels, self.transformer_blocks[0].attn2.heads)
 
-    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None, sag=None):
+    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None):
         """Returns alpha * (proj_out(...) + bias) + res, res defaulting to x (the block's own skip).
         alpha/res implement VD's context mixing sum_i r_i * ST_i(x) without extra passes.
         sync: callable invoked right before the ONE launch that reads `res` (the last of the block): the caller runs the blocks
@@ -361,7 +382,11 @@ class SpatialTransformer(nn.Module):
         tome: None, or (r, sink) of token merging (r > 0): this block's self-attention merges r tokens of its H x W grid, the metric
         being the h that enters the transformer block (at width 320 the one the chained entry kernel returns).
         sag: None, or a contiguous fp32 [n, H W] view, n <= B: the block's self-attention writes the column mass of its attention map
-        for the samples [0, n) into it (self-attention guidance); the block's output is untouched."""
+        for the samples [0, n) into it (self-attention guidance); the block's output is untouched.
+        tile: None, or (th, tw) of HyperTile: this block's self-attention runs inside th x tw tiles of its H x W grid
+        (CrossAttention.forward(tile=(H, W, th, tw))), under repeat > 1 too: once per guidance pair."""
+        if tile is not None:
+            tile = (x.shape[1], x.shape[2], int(tile[0]), int(tile[1]))
         if tome is not None:
             tome = (x.shape[1], x.shape[2], int(tome[0]), tome[1] if len(tome) > 1 else None)
         assert repeat == 1 or ident_from is None, "a perturbed replica takes the replicated input"
@@ -385,7 +410,8 @@ class SpatialTransformer(nn.Module):
             if pres.is_contiguous() and self.proj_out.out_channels == inner and self.proj_out.bias is not None:
                 wp, bp = self.proj_out._w()
                 post = (wp, bp, float(alpha), pres.view(B, H * W, C), H * W)
-            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome, sag=sag)
+            h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome, sag=sag,
+                    tile=tile)
             if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the block's last launch
                 out = h[0]
                 st = ops.stats_of(out)
@@ -408,7 +434,7 @@ class SpatialTransformer(nn.Module):
                 ff_post = (self.proj_out, float(alpha), pres, H * W)
         h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
                                        repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None, ident_from=ident_from,
-                                       tome=tome, sag=sag)
+                                       tome=tome, sag=sag, tile=tile)
         if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the feed-forward's output GEMM
             out = h[0]
             st = ops.stats_of(out)

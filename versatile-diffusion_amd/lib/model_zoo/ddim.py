@@ -21,8 +21,8 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import (DeepCache, _freeu_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
-                 kv_rows, sag_map_size, sag_taps, tome_blocks)
+from .vd import (DeepCache, _freeu_arg, _hypertile_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
+                 kv_rows, hypertile_blocks, sag_map_size, sag_taps, tome_blocks)
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -353,6 +353,9 @@ class DDIMSampler(object):
         # x_info['tome_ratio'] / ['tome_max_downsample'] (extension keys, vd._tome_arg): None, or the TokenMerge; raises like the
         # others.  The setting travels with every forward (_eps), like FreeU's
         tome = _tome_arg(x_info, self.model, shape)
+        # x_info['hypertile'] / ['hypertile_max_downsample'] (extension keys, vd._hypertile_arg): None, or the HyperTile; raises like
+        # the others.  It travels with every forward too (_eps)
+        hypertile = _hypertile_arg(x_info, self.model, shape)
         # x_info['sag_scale'] / ['sag_blur_sigma'] (extension keys, vd._sag_arg): None, or (s_sag, sigma); raises like the others
         sag = _sag_arg(x_info, self.model, shape)
         # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
@@ -414,6 +417,10 @@ class DDIMSampler(object):
             th, tw = (x.shape[2], x.shape[3]) if window is None else window["key"][:2]
             intermediates["tome_tokens"] = [(H * W, H * W - r) for _, H, W, r in
                                             tome_blocks(self.model.diffuser[x_info["type"]], th, tw, tome)]
+        if hypertile is not None:
+            th, tw = (x.shape[2], x.shape[3]) if window is None else window["key"][:2]
+            intermediates["hypertile_tiles"] = [(H * W, nty * ntx) for _, H, W, nty, ntx in
+                                                hypertile_blocks(self.model.diffuser[x_info["type"]], th, tw, hypertile)]
         x_info["x"] = x.to(dtype)
         return x_info["x"], intermediates
 
@@ -527,6 +534,8 @@ class DDIMSampler(object):
         identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward.
         x_info['tome_ratio'] / ['tome_max_downsample'] (token merging, vd._tome_arg) travel with every forward as apply_model*'s
         'tome', so with windows the merge acts on each window's token grid.
+        x_info['hypertile'] / ['hypertile_max_downsample'] (HyperTile, vd._hypertile_arg) travel the same way, as apply_model*'s
+        'hypertile': with windows the tiles are cut on each window's token grid.
         sag: None, or the fp32 [T, B, Nm] mass buffer of self-attention guidance (apply_model*'s 'sag'): the forward also writes the
         column mass of the middle block's self-attention map of replica 0 into it."""
         if window is not None:
@@ -549,6 +558,9 @@ class DDIMSampler(object):
         tome = _tome_arg(x_info, self.model)
         if tome is not None:
             xi["tome"] = tome
+        hypertile = _hypertile_arg(x_info, self.model)
+        if hypertile is not None:
+            xi["hypertile"] = hypertile
         if single:
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
@@ -661,7 +673,9 @@ class DDIMSampler(object):
         # decides the shapes behind them -- one graph per setting;
         # and self-attention guidance: a further entry ("sag",) at the END when it is on, nothing when it is off (the key of a call
         # without it is the key it always had): a graph captured with it runs the mass, the degrade, a second forward and the fold;
-        # its scale and sigma are not in the key -- weight and taps are loaded per call)
+        # its scale and sigma are not in the key -- weight and taps are loaded per call;
+        # and HyperTile, likewise: a further entry ("hypertile", tile, max_downsample) in front of sag's when it is on, nothing when it
+        # is off: the tile side is an argument of the captured tile / untile launches and decides the attention's shapes)
         pag = _pag_arg(x_info, self.model)
         tome = _tome_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
@@ -669,6 +683,9 @@ class DDIMSampler(object):
                tuple((ci["type"], tuple(ci["c"].shape), float(ci.get("ratio", 1.0))) for ci in c_info_list),
                inpaint is not None, mask_batch, rescale > 0., cache_depth, None if window is None else window["key"],
                None if tome is None else tome.key(), (pag is not None, None if pag is None else pag[1]), _freeu_arg(x_info))
+        hypertile = _hypertile_arg(x_info, self.model)
+        if hypertile is not None:
+            key = key + (("hypertile",) + hypertile.key(),)
         if _sag_arg(x_info, self.model) is not None:
             key = key + (("sag",),)
         return key
@@ -957,6 +974,7 @@ class DDIMSampler(object):
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         pag = _pag_arg(x_info, self.model)      # so is perturbed-attention guidance: one more replica and the fold
         _tome_arg(x_info, self.model, x_info["x"].shape)    # and token merging: the step's forward applies it (_eps)
+        _hypertile_arg(x_info, self.model, x_info["x"].shape)   # and HyperTile: the step's forward applies it (_eps)
         sag = _sag_arg(x_info, self.model, x_info["x"].shape)   # and self-attention guidance: the step runs its second forward
         assert not use_original_steps and not repeat_noise
         cis, guided, scale, phi = self._cfg_contexts(c_info_list, pag=pag is not None)

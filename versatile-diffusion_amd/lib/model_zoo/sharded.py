@@ -98,7 +98,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                       cache_interval=1, cache_depth=1, window=None, window_stride=None, window_wrap=False,
                       window_weight="uniform", window_batch=8, freeu=None, region_masks=None, pag_scale=None,
                       pag_layers=None, tome_ratio=None, tome_max_downsample=None, vae_tile=None, vae_tile_stride=None,
-                      vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None, sag_scale=None, sag_blur_sigma=None):
+                      vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None, sag_scale=None, sag_blur_sigma=None,
+                      hypertile=None, hypertile_max_downsample=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -132,6 +133,9 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     tome_ratio, tome_max_downsample: the samplers' x_info['tome_ratio'] and x_info['tome_max_downsample'] (token merging,
     vd._tome_arg; None = the key is not set).  The merge is per sample, so a rank's slice sees what the whole batch would.
+
+    hypertile, hypertile_max_downsample: the samplers' x_info['hypertile'] and x_info['hypertile_max_downsample'] (HyperTile,
+    vd._hypertile_arg; None = the key is not set).  The tiles are cut per sample, so a rank's slice sees what the whole batch would.
 
     region_masks: the samplers' x_info['region_masks'] (regional prompts on the windowed path, ddim._window_args; None = off, and
     then the key is not set; it needs `window`).  A context's 'conditioning' may then be a list of one [B, L, D] tensor per
@@ -191,6 +195,10 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             x_info["tome_ratio"] = tome_ratio
         if tome_max_downsample is not None:
             x_info["tome_max_downsample"] = tome_max_downsample
+        if hypertile is not None:
+            x_info["hypertile"] = hypertile
+        if hypertile_max_downsample is not None:
+            x_info["hypertile_max_downsample"] = hypertile_max_downsample
         from .dpm_solver import DPMSolverSDESampler
         if isinstance(sampler, DPMSolverSDESampler):
             world = dist.get_world_size(group) if dist.is_initialized() else 1

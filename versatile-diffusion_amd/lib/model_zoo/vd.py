@@ -513,6 +513,120 @@ def _tome_fwd_arg(x_info):
     return tm
 
 
+# ---- HyperTile (x_info['hypertile'], x_info['hypertile_max_downsample']; the forward key is x_info['hypertile'] too) -------------
+# tfernd, "HyperTile: Tiled-optimizations for Stable-Diffusion" (2023; shipped in ComfyUI, A1111 and SD.Next) with scale_depth and a
+# FIXED divisor: the original draws the divisor of a level at random per call, here the tile side is the same at every level and in
+# every call, which keeps one step graph per setting and run-to-run identical bits.  In the context blocks after k Downsamples,
+# 2^k <= max_downsample, the self-attention runs inside square tiles of the token grid: CrossAttention.forward(tile=...), contract in
+# include/vd_hip.h.  An approximation like token merging and DeepCache, meant for canvases larger than the trained size.
+class HyperTile(object):
+    """The setting of HyperTile: tile, the side of a square tile in tokens (an int >= 2, the same at every level), and
+    max_downsample, 1, 2 or 4.  ValueError (matching 'hypertile') for anything else."""
+
+    def __init__(self, tile, max_downsample=1):
+        if isinstance(tile, (bool, np.bool_)) or not isinstance(tile, (int, np.integer)) or int(tile) < 2:
+            raise ValueError("hypertile must be an int >= 2 (the tile side in tokens), got %r" % (tile,))
+        if isinstance(max_downsample, (bool, np.bool_)) or not isinstance(max_downsample, (int, np.integer)) \
+                or int(max_downsample) not in (1, 2, 4):
+            raise ValueError("hypertile_max_downsample must be 1, 2 or 4, got %r" % (max_downsample,))
+        self.tile = int(tile)
+        self.max_downsample = int(max_downsample)
+
+    def key(self):
+        return self.tile, self.max_downsample
+
+
+def hypertile_blocks(net, H0, W0, ht):
+    """[(walk index of the context block, H, W, nty, ntx)] of the blocks of the 2-D data net `net` whose self-attention is tiled
+    under the HyperTile `ht` on an H0 x W0 latent, in walk order.  A block after k Downsamples, 2^k <= ht.max_downsample, has the
+    grid H0 / 2^k x W0 / 2^k (every Downsample halves a side, rounding up); a grid that fits in one tile (H, W <= tile) is absent:
+    that block runs the untiled path.  ValueError (matching 'hypertile') for a net without such a walk and for a grid larger than
+    one tile with a side that is not a multiple of the tile."""
+    from .openaimodel import Downsample, UNetModel0D_Next, Upsample
+    if isinstance(net, UNetModel0D_Next) or not all(hasattr(net, k) for k in ("i_order", "m_order", "o_order", "data_blocks")):
+        raise ValueError("hypertile needs a 2-D data net (x_info['type'] == 'image'), got %s" % type(net).__name__)
+    d_iter = iter(net.data_blocks)
+    sizes = [(int(H0), int(W0))]        # the grid per level, as the way down produced it
+    level, ci, out = 0, 0, []
+    for s in list(net.i_order) + list(net.m_order) + list(net.o_order):
+        if s == "d":
+            blk = next(d_iter)
+            if any(isinstance(m, Downsample) for m in blk.modules()):
+                level += 1
+                if level == len(sizes):
+                    sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+            elif any(isinstance(m, Upsample) for m in blk.modules()):
+                level -= 1
+        elif s == "c":
+            H, W = sizes[level]
+            if 2 ** level <= ht.max_downsample and (H > ht.tile or W > ht.tile):
+                if H % ht.tile or W % ht.tile:
+                    raise ValueError("hypertile: the tile side %d does not divide the %d x %d token grid of level %d of a %d x %d "
+                                     "latent (or window)" % (ht.tile, H, W, level, H0, W0))
+                out.append((ci, H, W, H // ht.tile, W // ht.tile))
+            ci += 1
+    return out
+
+
+def _hypertile_arg(x_info, model, shape=None):
+    """The sampler keys of HyperTile validated: None when x_info['hypertile'] is absent, None or 0 (off: today's call), else the
+    HyperTile(x_info['hypertile'], x_info.get('hypertile_max_downsample', 1)); a ready HyperTile is taken as it is.  ValueError
+    (matching 'hypertile') for a bool, a non-int or a side < 2, a max_downsample other than 1, 2 or 4, another flow than the 2-D image
+    flow, tome_ratio in the same call and, when `shape` ([B, C, H, W]) is given, a latent -- or with x_info['window'] a window --
+    with a tiled level the tile does not divide, and self-attention guidance whose map block would be tiled.  Perturbed-attention
+    guidance combines: a perturbed layer that is also tiled keeps its identity rows.  Touches no device."""
+    value = x_info.get("hypertile")
+    md = x_info.get("hypertile_max_downsample")
+    if isinstance(value, HyperTile):
+        if md is not None and md != value.max_downsample:
+            raise ValueError("x_info holds a ready HyperTile in 'hypertile' and another 'hypertile_max_downsample': pass one")
+        ht = value
+    else:
+        if value is None or (not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, np.integer)) and int(value) == 0):
+            if md is not None:
+                HyperTile(2, md)
+            return None
+        ht = HyperTile(value, 1 if md is None else md)
+    if x_info.get("type") != "image":
+        raise ValueError("hypertile applies to x_info['type'] == 'image' only (self-attention over a token grid), got %r"
+                         % (x_info.get("type"),))
+    if x_info.get("tome_ratio") not in (None, 0, 0.) or x_info.get("tome") is not None:
+        raise ValueError("hypertile with tome_ratio is out of scope on purpose: one plan per self-attention")
+    if shape is not None:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 4:
+            raise ValueError("hypertile: the latent shape must be [B, C, H, W], got %s" % (shape,))
+        H, W = shape[2:]
+        if x_info.get("window") is not None:
+            from . import windows
+            h, w = windows.int_pair("window", x_info["window"])
+            H, W = min(h, H), min(w, W)
+        net = model.diffuser[x_info["type"]]
+        blocks = hypertile_blocks(net, H, W, ht)
+        if x_info.get("sag_scale") not in (None, 0, 0.) and pag_context_blocks(net)[1] in [b[0] for b in blocks]:
+            raise ValueError("hypertile would tile the block self-attention guidance reads its map from (sag_scale): lower "
+                             "hypertile_max_downsample or raise the tile side")
+    return ht
+
+
+def _hypertile_fwd_arg(x_info):
+    """x_info['hypertile'] as apply_model* sees it (set by the samplers) validated: None (absent, None or 0), or the HyperTile -- an
+    int side is taken with x_info.get('hypertile_max_downsample', 1), like the sampler key."""
+    value = x_info.get("hypertile")
+    if value is None:
+        return None
+    if not isinstance(value, HyperTile):
+        if not isinstance(value, (bool, np.bool_)) and isinstance(value, (int, np.integer)) and int(value) == 0:
+            return None
+        md = x_info.get("hypertile_max_downsample")
+        value = HyperTile(value, 1 if md is None else md)
+    if x_info.get("type") != "image":
+        raise ValueError("hypertile applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if x_info.get("tome") is not None:
+        raise ValueError("hypertile with tome is out of scope on purpose: one plan per self-attention")
+    return value
+
+
 # ---- self-attention guidance (x_info['sag_scale'], x_info['sag_blur_sigma']; forward key x_info['sag']) ------------------------
 # Hong et al., "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance" (ICCV 2023); diffusers'
 # StableDiffusionSAGPipeline(sag_scale).  A forward with x_info['sag'] also writes the column mass of the middle context block's
@@ -629,7 +743,7 @@ def kv_rows(cache, rows):
 
 
 def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None,
-             tome=None, sag=None):
+             tome=None, sag=None, hypertile=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -662,7 +776,22 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     for the rows [0, B) of the batch -- replica 0 -- type t's module into sag[t], on the stream that module runs on (the joins of the
     forked branches order the writes before the next launch on the caller's stream); a half-batch branch holding samples [b0, b1)
     writes the rows [b0, min(b1, B)).  Nothing else changes: the eps bits are those of the forward without it.  It does not combine
-    with tome or deep (ValueError)."""
+    with tome or deep (ValueError).
+    hypertile: None, or a HyperTile: the context blocks of hypertile_blocks (every context type's block at those walk indices) run
+    their self-attention inside square tiles of their token grid (SpatialTransformer.forward(tile=(side, side))), the block that
+    takes a guided batch un-replicated too.  Every other block, and a forward without it, keeps today's launches and bits.  It
+    combines with pag (a perturbed layer that is tiled keeps its identity rows), deep and freeu; not with tome, nor with a sag whose
+    map block is tiled (ValueError)."""
+    hmap = None
+    if hypertile is not None:
+        if x.dim() != 4:
+            raise ValueError("hypertile needs a 2-D data net (x_info['type'] == 'image')")
+        if tome is not None:
+            raise ValueError("hypertile does not combine with tome")
+        hmap = {b[0] for b in hypertile_blocks(data_net, x.shape[-2], x.shape[-1], hypertile)}
+        if sag is not None and pag_context_blocks(data_net)[1] in hmap:
+            raise ValueError("hypertile would tile the block sag reads its map from")
+        hmap = (hmap, (hypertile.tile, hypertile.tile)) if hmap else None
     smap = None
     if sag is not None:
         if x.dim() != 4:
@@ -736,16 +865,19 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None, sag=None):
+    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
         repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them.
         ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag).
         tome: None, or (r, sink) of token merging for these blocks' self-attention.
-        sag: None, or the mass buffer [T, B, Nm] of self-attention guidance: module t writes the rows of replica 0 that h holds."""
+        sag: None, or the mass buffer [T, B, Nm] of self-attention guidance: module t writes the rows of replica 0 that h holds.
+        tile: None, or (th, tw) of HyperTile for these blocks' self-attention."""
         single = len(modules) == 1
         pkw = {} if ident_from is None else {"ident_from": int(ident_from)}
         if tome is not None:
             pkw["tome"] = tome
+        if tile is not None:
+            pkw["tile"] = tile
         skw = [{} for _ in modules]
         if sag is not None:
             lo, hi = (0, sag.shape[1]) if sl is None else (sl[0], min(sl[1], sag.shape[1]))
@@ -812,7 +944,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
                               h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
-                              fmap or None, pag, tmap, smap)
+                              fmap or None, pag, tmap, smap, hmap)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -853,8 +985,8 @@ def _fork_region(steps, hw0, thr):
 
 
 def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None,
-                   pag=None, tome=None, sag=None):
-    """sag: None, or (walk index of the middle stage's first context block, the mass buffer) of run_unet.  deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
+                   pag=None, tome=None, sag=None, hypertile=None):
+    """hypertile: None, or ({walk index of a tiled context block}, (th, tw)) of run_unet.  sag: None, or (walk index of the middle stage's first context block, the mass buffer) of run_unet.  deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
     the active FreeU stages.  pag: None, or (layers, row0) of run_unet.  tome: None, or ({walk index of a merging context block: r},
     the TokenMerge's record list or None)."""
     state = {"shared": shared}
@@ -883,16 +1015,17 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                     else:
                         h = rep(h)
                     state["shared"] = False
+                tkw = {} if hypertile is None or st[4] not in hypertile[0] else {"tile": hypertile[1]}
                 if pag is not None and st[4] in pag[0]:
                     b0, b1 = (0, h.shape[0]) if sl is None else sl
-                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, ident_from=min(max(pag[1] - b0, 0), b1 - b0))
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, ident_from=min(max(pag[1] - b0, 0), b1 - b0), **tkw)
                 elif tome is not None and st[4] in tome[0]:
                     sink = None if tome[1] is None else (lambda row_of, ci=st[4], rec=tome[1]: rec.append((ci, row_of.clone())))
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, tome=(tome[0][st[4]], sink))
                 elif sag is not None and st[4] == sag[0]:
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, sag=sag[1])
                 else:
-                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share)
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, **tkw)
             elif st[0] == "save":
                 hs.append(h)
             elif st[0] == "load":
@@ -1123,11 +1256,13 @@ class VD_v2_0(nn.Module):
         freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])   # extension key: (layers, row0), see run_unet
         tome = _tome_fwd_arg(x_info)    # extension key: a TokenMerge, see run_unet
+        hypertile = _hypertile_fwd_arg(x_info)      # extension key: a HyperTile, see run_unet
         sag = _sag_fwd_arg(x_info, 1)   # extension key: the fp32 [1, B, Nm] mass buffer of self-attention guidance, see run_unet
         emb = self._emb_silu(glayer_ptr, timesteps) if rows is None else None
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
-                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome, sag=sag).to(x.dtype)
+                        emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome, sag=sag,
+                        hypertile=hypertile).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -1139,6 +1274,7 @@ class VD_v2_0(nn.Module):
         freeu = _freeu_arg(x_info)
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])
         tome = _tome_fwd_arg(x_info)
+        hypertile = _hypertile_fwd_arg(x_info)
         sag = _sag_fwd_arg(x_info, len(c_info_list))
         # reference takes time_embed from diffuser[x_type] here (vd.py:415-417)
         emb = self._emb_silu(x_type, timesteps) if rows is None else None
@@ -1146,4 +1282,4 @@ class VD_v2_0(nn.Module):
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
                         repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag,
-                        tome=tome, sag=sag).to(x.dtype)
+                        tome=tome, sag=sag, hypertile=hypertile).to(x.dtype)

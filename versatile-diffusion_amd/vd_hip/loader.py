@@ -133,6 +133,8 @@ PROTOTYPES = {
     "vd_tome_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "vd_tome_merge_f16": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _I, _P, _I, _L, _P]),
     "vd_tome_unmerge_f16": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _I, _P, _I, _L, _P]),
+    "vd_tile_tokens_f16": (_I, [_P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_untile_tokens_f16": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P]),
     "vd_q_sample_f16": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),
     "vd_nchw_to_nhwc_f16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "vd_nhwc_to_nchw_f16": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _I, _P]),

@@ -1667,6 +1667,47 @@ def tome_unmerge(a, row_of, H, W, r, out=None):
     return out
 
 
+def _tile_grid(what, H, W, th, tw):
+    for v in (H, W, th, tw):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise VdHipError("%s: the grid %r x %r and the tile %r x %r must be ints" % (what, H, W, th, tw))
+
+
+def tile_tokens(x, H, W, th, tw):
+    """HyperTile gather (vd_tile_tokens_f16, contract in include/vd_hip.h): x [B, H W, cols] fp16 with unit inner stride (the fused
+    q | k | v of a block, a column or a batch slice of it) -> contiguous [B (H / th) (W / tw), th tw, cols]: every th x tw tile of
+    the token grid becomes a sample of its own.  A bit-exact copy, one launch."""
+    _tome_rows(x, "x")
+    _tile_grid("tile_tokens", H, W, th, tw)
+    B, N, cols = x.shape
+    if H * W != N or th <= 0 or tw <= 0:
+        raise VdHipError("tile_tokens: the grid %d x %d (tile %d x %d) does not hold the %d rows of a sample" % (H, W, th, tw, N))
+    out = torch.empty((B * (H // th) * (W // tw), th * tw, cols), dtype=torch.float16, device=x.device)
+    with _Timed("hypertile_rows_kernel<tile>", 0.0, 4.0 * B * N * cols):
+        _check(lib().vd_tile_tokens_f16(_ptr(x), x.stride(1), x.stride(0), cols, B, H, W, th, tw, _ptr(out), _stream()))
+    return out
+
+
+def untile_tokens(a, B, H, W, th, tw, out=None):
+    """HyperTile scatter (vd_untile_tokens_f16): the exact inverse of tile_tokens: a contiguous [B (H / th) (W / tw), th tw, cols]
+    fp16 -> [B, H W, cols] (`out`, when given, may be a view with unit inner stride).  A bit-exact copy, one launch."""
+    _req(a, "a")
+    _tile_grid("untile_tokens", H, W, th, tw)
+    if isinstance(B, bool) or not isinstance(B, int) or th <= 0 or tw <= 0 or a.dim() != 3 \
+            or tuple(a.shape[:2]) != (B * (H // th) * (W // tw), th * tw):
+        raise VdHipError("untile_tokens: a %s is not the %d samples of a %d x %d grid in tiles of %d x %d" % (tuple(a.shape), B, H, W, th, tw))
+    cols = a.shape[2]
+    if out is None:
+        out = torch.empty((B, H * W, cols), dtype=torch.float16, device=a.device)
+    else:
+        _tome_rows(out, "out")
+        if tuple(out.shape) != (B, H * W, cols):
+            raise VdHipError("untile_tokens: out %s is not [%d, %d, %d]" % (tuple(out.shape), B, H * W, cols))
+    with _Timed("hypertile_rows_kernel<untile>", 0.0, 4.0 * B * H * W * cols):
+        _check(lib().vd_untile_tokens_f16(_ptr(a), cols, B, H, W, th, tw, _ptr(out), out.stride(1), out.stride(0), _stream()))
+    return out
+
+
 def q_sample(x0, noise, sa, sb):
     _req(x0, "x0"); _req(noise, "noise"); _req(sa, "sa", torch.float32); _req(sb, "sb", torch.float32)
     out = torch.empty_like(x0)
@@ -1898,7 +1939,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "tile_tokens", "untile_tokens", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
