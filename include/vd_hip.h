@@ -774,6 +774,42 @@ int vd_sag_degrade_f16(const void* x, const void* eps0, const float* mass, const
                        const float* coef, void* xd, int B, int C, int H, int W, int Hm, int Wm, hipStream_t stream);
 int vd_sag_fold_f16(void* eps, const void* e_d, int64_t n, const float* w, hipStream_t stream);
 
+/* Adaptive projected guidance (Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in
+ * Diffusion Models", 2024, Algorithm 1; diffusers' AdaptiveProjectedGuidance(eta, norm threshold, momentum); not in the reference).
+ * The guidance direction, taken between the DATA predictions, gets a momentum across steps, has its norm clipped per sample, and
+ * loses the share (1 - eta) of its part parallel to the conditional data prediction.  One entry point (additive to ABI 8), one
+ * launch per step, in front of the unchanged update.
+ *
+ * vd_apg_fold_f16: x is fp16 [n] (the latent); eps is fp16 with the leading [2][n] = [e_u ; e_c], of which only the leading [n] is
+ * written; v is fp32 [n], the running direction (read only when coef[3] != 0, always written); coef is fp32 [8] in DEVICE memory,
+ * {s1, isa, ig, beta_eff, r, 1 - eta, 0, 0} with s1 = sqrt(1 - a_t), isa = 1 / sqrt(a_t), ig = 1 / (s1 isa), each formed in double
+ * and rounded once by the host (one captured launch serves every step and setting); fac is fp32 [n / per_sample][4].
+ * For sample b with m = per_sample elements (its flattened [C, *spatial] latent), per element, each line ONE fp32 operation:
+ *     D   = fmaf(-s1, e_c, x) * isa               the conditional data prediction: one fma, one multiplication
+ *     dD  = (-g32) * (e_c - e_u)                  g32 = s1 * isa rounded once; one subtraction, one multiplication (= D_c - D_u)
+ *     v   = fmaf(beta_eff, v_prev, dD)            or v = dD when beta_eff == 0 (v_prev is then not read: it may hold anything)
+ * over the sample, in fp64 (the product of two fp32 values is exact there), then rounded ONCE to fp32 where they are used:
+ *     Svv = sum v^2,  Svd = sum v D,  Sdd = sum D^2
+ *     k   = min(1, r / sqrt(Svv)),  1 when r == 0 or Svv == 0                    the norm threshold, in units of the data prediction
+ *     p   = k Svd / Sdd,  0 when Sdd == 0;      q = (1 - eta) p                  the parallel coefficient and the share removed
+ *     fac[b] = {(float)sqrt(Svv), (float)k, (float)p, (float)sqrt(Sdd)}
+ * and per element again, with k and q as fp32:
+ *     nn  = fmaf(-q, D, k * v)                    one multiplication, one fma: the orthogonal part + eta times the parallel part
+ *     e_u = fp16(fmaf(nn, ig, e_c))               one fma, then a rounding of its own to fp16, to nearest even
+ * The unchanged update then forms e_u' + s (e_c - e_u') = e_c - (s - 1) nn / g, the epsilon form of D_c + (s - 1) nn; the fold does
+ * not read s.  With eta = 1, r = 0, beta_eff = 0 it writes e_u back (up to the roundings above): plain guidance.  Downstream
+ * nothing changes: vd_cfg_rescale_factor_f16 (which keeps targeting the standard deviation of e_c) and every vd_cfg_*_step_* run on
+ * the folded pair; vd_pag_fold_f16 runs after this fold and only adds to replica 0, so the two compose additively.
+ * One block reduces and rewrites a sample, whatever the batch, in an order that depends on per_sample alone (per-lane fp64 sums, a
+ * fixed butterfly over the wave, the waves added in order; no atomics; the same lane handles the same elements before and after the
+ * block barrier), so a sample's fac, v and e_u are a pure function of its operands and coef: the same bits for any batch size,
+ * batch position, alignment (16-byte accesses when x, both replicas and v of the sample are 16-byte aligned, else element-wise
+ * accesses of the same elements with the same arithmetic), graph or rank.  Any per_sample.  Neither allocates nor synchronises
+ * (capturable).  Returns < 0 (vd_last_error, the text starts with this entry's name) for null pointers, n or per_sample <= 0, n not
+ * a multiple of per_sample, or x / eps / v / coef / fac not aligned to their element size. */
+int vd_apg_fold_f16(const void* x, void* eps, float* v, const float* coef, float* fac, int64_t n, int64_t per_sample,
+                    hipStream_t stream);
+
 /* Token merging for self-attention (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion", 2023; the tomesd package with
  * sx = sy = 2, use_rand = False; not in the reference).  Four entry points (additive to ABI 8); none allocates or synchronises
  * (capturable).  Every one returns < 0 (vd_last_error, the text starts with the entry's name) for null pointers, an empty problem,

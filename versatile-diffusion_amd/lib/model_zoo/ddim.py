@@ -21,7 +21,7 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import (DeepCache, _freeu_arg, _hypertile_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
+from .vd import (DeepCache, _apg_arg, _freeu_arg, _hypertile_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
                  kv_rows, hypertile_blocks, sag_map_size, sag_taps, tome_blocks)
 
 
@@ -237,6 +237,53 @@ def sag_ratios(c_info_list):
     return (r / r.sum()).astype(np.float32)
 
 
+def apg_coef_table(alphas_cumprod, timesteps, eta, r, beta):
+    """fp32 [S, 8] rows {s1, isa, 1 / g, beta_eff, r, 1 - eta, 0, 0} of ops.apg_fold per DDIM index i (the row the loops copy next
+    to their coefficient row), a_t = alphas_cumprod[timesteps[i]], s1 = sqrt(1 - a_t), isa = 1 / sqrt(a_t), g = s1 isa, every entry
+    formed in float64 and rounded once.  `timesteps` are the steps THIS call runs (a start from x_info['xt'] or
+    ['x0_forward_timesteps'] runs the leading ones only): the loops walk the indices downwards, so the row of the first step a call
+    runs is the LAST one, and it has beta_eff = 0 -- the running direction starts there and the state is not read; every other
+    row has beta_eff = beta."""
+    a = np.asarray(alphas_cumprod, dtype=np.float64)[np.asarray(timesteps, dtype=np.int64)]
+    s1, isa = np.sqrt(1.0 - a), 1.0 / np.sqrt(a)
+    tab = np.zeros((a.shape[0], 8), dtype=np.float64)
+    tab[:, 0], tab[:, 1], tab[:, 2] = s1, isa, 1.0 / (s1 * isa)
+    tab[:, 3], tab[:, 4], tab[:, 5] = float(beta), float(r), 1.0 - float(eta)
+    if a.shape[0]:
+        tab[-1, 3] = 0.0
+    return tab.astype(np.float32)
+
+
+def apg_guided_eps(x, eps, v_prev, row):
+    """The float64 statement of adaptive projected guidance (Sadat et al. 2024, Algorithm 1, written for an epsilon model; the
+    contract of vd_apg_fold_f16 in include/vd_hip.h without its roundings).  x [B, ...] the latent, eps = [e_uncond ; e_cond]
+    ([2B, ...]), v_prev [B, ...] the running direction of the step before (None, or anything when row[3] == 0: not read), row the
+    step's {s1, isa, 1 / g, beta_eff, r, 1 - eta, ...} (apg_coef_table).  Per sample, with g = s1 isa and sums over its elements:
+
+        D_c = (x - s1 e_c) isa;  dD = -g (e_c - e_u);  v = dD + beta_eff v_prev
+        k = min(1, r / ||v||), 1 if r == 0 or ||v|| == 0;  p = k <v, D_c> / <D_c, D_c>, 0 if <D_c, D_c> == 0;  q = (1 - eta) p
+        n = k v - q D_c;  e_u' = e_c + n row[2]
+
+    Returns (e_u' [B, ...], v [B, ...], fac [B, 4] = {||v||, k, p, ||D_c||}), all float64.  The update's e_u' + s (e_c - e_u') is
+    e_c - (s - 1) n / g, the epsilon form of D_c + (s - 1) n; (eta, r, beta) = (1, 0, 0) returns e_u."""
+    s1, isa, ig, beta, r, ome = [float(v) for v in list(row)[:6]]
+    eu, ec = eps.detach().double().chunk(2)
+    x = x.detach().double()
+    g = s1 * isa
+    D = (x - s1 * ec) * isa
+    v = -g * (ec - eu)
+    if beta != 0.:
+        v = v + beta * v_prev.detach().double()
+    dot = lambda a, b: (a * b).flatten(1).sum(1)
+    svv, svd, sdd = dot(v, v), dot(v, D), dot(D, D)
+    nv, one = torch.sqrt(svv), torch.ones_like(svv)
+    k = torch.where(nv > 0, (r / torch.where(nv > 0, nv, one)).clamp(max=1.0), one) if r != 0. else one
+    p = torch.where(sdd > 0, k * svd / torch.where(sdd > 0, sdd, one), torch.zeros_like(sdd))
+    col = lambda t: t.view(-1, *([1] * (x.dim() - 1)))
+    n = col(k) * v - col(ome * p) * D
+    return ec + n * ig, v, torch.stack([nv, k, p, torch.sqrt(sdd)], dim=1)
+
+
 _gc_lock = threading.Lock()
 _gc_holds = [0, False]      # captures in progress in this process; whether the collector was on when the first began
 
@@ -358,12 +405,17 @@ class DDIMSampler(object):
         hypertile = _hypertile_arg(x_info, self.model, shape)
         # x_info['sag_scale'] / ['sag_blur_sigma'] (extension keys, vd._sag_arg): None, or (s_sag, sigma); raises like the others
         sag = _sag_arg(x_info, self.model, shape)
+        # x_info['apg_eta'] / ['apg_norm_threshold'] / ['apg_momentum'] (extension keys, vd._apg_arg): None, or (eta, r, beta);
+        # raises like the others
+        apg = _apg_arg(x_info)
         # regional prompts: from here on the contexts are the flat region-major list, one conditioning tensor each
         c_info_list = _region_contexts(c_info_list, window, shape[0])
         # CFG batch [uncond ; cond] assembled ONCE; K/V projections of it cached for the whole loop.  First, so that a bad
         # guidance_rescale raises like a bad mask: before anything is drawn
         device = self.model.device
         c_info_list, guided, scale, phi = self._cfg_contexts(c_info_list, 1 if window is None else window["m"], pag is not None)
+        if not guided:
+            apg = None      # there is no guidance direction to project: an unguided call ignores the keys, like the rescale
         dtype = c_info_list[0]["conditioning"].dtype
         x_info["x"], timesteps, blend_noise = self._start_latent(shape, x_info, masked, device, dtype)
         inpaint = None
@@ -381,9 +433,15 @@ class DDIMSampler(object):
         # generator on every step, between the noise draws: that order only exists in the eager loop
         if x.is_cuda and eta_zero and total_steps > 0 and not noise_dropout > 0.:
             x, intermediates = self._loop_static(x, x_info, c_info_list, timesteps, guided, scale, _single, log_every_t, dtype,
-                                                 inpaint, phi, interval, depth, window, pag, sag)
+                                                 inpaint, phi, interval, depth, window, pag, sag, apg)
         else:
             intermediates = {"pred_xt": [], "pred_x0": []}
+            apg_step = None
+            if apg is not None:     # per-call buffers; row `index` of the table is the step's coefficient row
+                apg_step = {"v": torch.empty(x.shape, device=x.device, dtype=torch.float32),
+                            "tab": torch.from_numpy(apg_coef_table(self.alphas_cumprod, timesteps, *apg)).to(x.device),
+                            "fac": torch.empty((x.shape[0], 4), device=x.device, dtype=torch.float32)}
+                intermediates["apg"] = []
             deep = DeepCache(depth) if interval > 1 else None
             wstate = None if window is None else self._window_state(window, x, guided, pag is not None)      # once per call
             pag_step = None if pag is None else (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)),
@@ -399,7 +457,8 @@ class DDIMSampler(object):
                 x, pred_x0, kfac = self._step(x, x_info, c_info_list, int(step), index, guided, scale, temperature, _single,
                                               noise_dropout=noise_dropout, rescale=rescale,
                                               deep=None if deep is None else (deep, "store" if i % interval == 0 else "reuse"),
-                                              window=wstate, pag=pag_step, sag=sag_step)
+                                              window=wstate, pag=pag_step, sag=sag_step,
+                                              apg=None if apg_step is None else (apg_step["v"], apg_step["tab"][index], apg_step["fac"]))
                 if inpaint is not None:
                     ops.masked_blend(x, inpaint["x0"], inpaint["noise"], inpaint["mask"], inpaint["table"][index], out=x)
                 if index % log_every_t == 0 or index == total_steps - 1:
@@ -407,6 +466,8 @@ class DDIMSampler(object):
                     intermediates["pred_x0"].append(pred_x0.to(dtype))
                     if kfac is not None:
                         intermediates["guidance_rescale"].append(kfac)
+                    if apg_step is not None:
+                        intermediates["apg"].append(apg_step["fac"].clone())
         if interval > 1:
             intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
         if pag is not None:
@@ -614,7 +675,7 @@ class DDIMSampler(object):
         return torch.from_numpy(tab.astype(np.float32)).to(device)
 
     # ---- the static step loop ----------------------------------------------------------------------------
-    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None, pag=False, sag=False):
+    def _new_state(self, x, c_info_list, guided, inpaint, rescale=0., cache_depth=0, window=None, pag=False, sag=False, apg=False):
         """Everything a captured step dereferences: latent buffers, step scalars, the CFG context batches and their K/V
         projections, the sampler's own buffers (_extra_static), when inpainting x0 / noise / mask / blend, and with the guidance
         rescale its weight "phi" (fp32 [1], loaded per call: one graph serves every positive weight) and the factors "kfac"
@@ -625,7 +686,9 @@ class DDIMSampler(object):
         of replica_count(guided, pag) replicas, and "pag_w" is the fold's weight (fp32 [1], loaded per call: one graph serves
         every positive pag_scale and every guidance scale).  sag (self-attention guidance on): "sag" holds the buffers of
         _sag_buffers; its weight, taps and ratios are loaded per call, its coefficients per step: one graph serves every sag_scale,
-        sigma and guidance scale."""
+        sigma and guidance scale.  apg (adaptive projected guidance on): "apg_v" is the running direction (fp32, like the latent),
+        "apg_coef" the fold's row (fp32 [8], loaded per step) and "apg_fac" its per-sample figures (fp32 [B, 4], written by every
+        step): one graph serves every eta, threshold, momentum and guidance scale."""
         nb = replica_count(guided, pag) * x.shape[0] * (1 if window is None else window["m"])
         st = {"xs": torch.empty_like(x), "x_next": torch.empty_like(x), "p0": torch.empty_like(x),
               "ts": torch.empty((nb,), device=x.device, dtype=torch.long),
@@ -641,6 +704,10 @@ class DDIMSampler(object):
             st["pag_w"] = torch.empty((1,), device=x.device, dtype=torch.float32)
         if sag:
             st["sag"] = self._sag_buffers(x, len(c_info_list))
+        if apg:
+            st.update(apg_v=torch.empty(x.shape, device=x.device, dtype=torch.float32),
+                      apg_coef=torch.empty((8,), device=x.device, dtype=torch.float32),
+                      apg_fac=torch.empty((x.shape[0], 4), device=x.device, dtype=torch.float32))
         if rescale > 0.:
             st.update(phi=torch.empty((1,), device=x.device, dtype=torch.float32),
                       kfac=torch.empty((x.shape[0],), device=x.device, dtype=torch.float32))
@@ -675,7 +742,10 @@ class DDIMSampler(object):
         # without it is the key it always had): a graph captured with it runs the mass, the degrade, a second forward and the fold;
         # its scale and sigma are not in the key -- weight and taps are loaded per call;
         # and HyperTile, likewise: a further entry ("hypertile", tile, max_downsample) in front of sag's when it is on, nothing when it
-        # is off: the tile side is an argument of the captured tile / untile launches and decides the attention's shapes)
+        # is off: the tile side is an argument of the captured tile / untile launches and decides the attention's shapes;
+        # and adaptive projected guidance, likewise: a further entry ("apg",) at the very end when it is on (a guided call whose
+        # triple is not the neutral one), nothing when it is off: a graph captured with it launches the fold; eta, threshold and
+        # momentum are not in the key -- the fold's row is loaded per step)
         pag = _pag_arg(x_info, self.model)
         tome = _tome_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
@@ -688,10 +758,12 @@ class DDIMSampler(object):
             key = key + (("hypertile",) + hypertile.key(),)
         if _sag_arg(x_info, self.model) is not None:
             key = key + (("sag",),)
+        if guided and _apg_arg(x_info) is not None:
+            key = key + (("apg",),)
         return key
 
     def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False,
-                      sag=False):
+                      sag=False, apg=False):
         """The state (_new_state) kept ACROSS sample() calls per (model weights, shapes, flow): a second call with the same
         geometry re-uses the instantiated HIP graph instead of capturing again (capture = one host-bound pass over ~400
         launches with the GPU idle + instantiation: 10-15 ms per batch of 680).  None when graphs are not kept."""
@@ -702,7 +774,7 @@ class DDIMSampler(object):
         if st is None:
             while len(self._static) >= 2:                      # shapes seen long ago: let their graphs go
                 self._static.pop(next(iter(self._static)))
-            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag, sag)
+            st = self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag, sag, apg)
         self._static[key] = st                                 # most recently used last
         return st
 
@@ -760,7 +832,7 @@ class DDIMSampler(object):
         return emb_tab, {di: st["embrow"][o:o + c] for di, (o, c) in layout.items()}
 
     def _loop_static(self, x, x_info, c_info_list, timesteps, guided, scale, single, log_every_t, dtype, inpaint=None,
-                     phi=0., interval=1, depth=1, window=None, pag=None, sag=None):
+                     phi=0., interval=1, depth=1, window=None, pag=None, sag=None, apg=None):
         """eta = 0 loop on static buffers: step 0 runs eagerly (fills weight-pack and K/V caches), is then captured
         into a HIP graph, and the graph is replayed for the remaining steps -- and, through _static_state, by later
         sample() calls of the same geometry.  Returns (final fp16 latent, intermediates).
@@ -776,7 +848,11 @@ class DDIMSampler(object):
         sag (None, or (s_sag, sigma) of vd._sag_arg): the step runs TWO forwards in sequence in the one captured graph -- the first,
         today's, also writes the column mass of the middle block's self-attention map; ops.sag_degrade blurs and re-noises the latent
         with it; the second forward predicts from that on one replica; ops.sag_fold folds its prediction into replica 0 (_sag_fold) --
-        and then the unchanged update, like pag's."""
+        and then the unchanged update, like pag's.
+        apg (None, or (eta, r, beta) of vd._apg_arg; guided calls only): ops.apg_fold rewrites replica 0 right behind the forward,
+        in front of pag's fold, from the latent, the pair and the running direction kept in the state (apg_guided_eps); the row of
+        apg_coef_table is copied next to the coefficient row, so one kept graph serves every setting; the update, the rescale
+        factors, the blend, the noise and the histories see the folded pair, so every sampler on this loop gets it."""
         tome = _tome_arg(x_info, self.model)
         if tome is not None and tome.record is not None and self.use_graph:
             raise ValueError("tome: TokenMerge.record is an eager-only hook; this loop captures its steps into a graph (use_graph)")
@@ -784,12 +860,15 @@ class DDIMSampler(object):
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
         st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pag is not None,
-                                 sag is not None)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None, sag is not None))
+                                 sag is not None, apg is not None)
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None, sag is not None,
+                                 apg is not None))
         replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window,
                                         None if pag is None else pag_weight(scale, pag[0], guided),
                                         None if sag is None else (sag[0], sag[1], scale, guided))
         sag_tab = None if sag is None else torch.from_numpy(sag_coef_table(self.alphas_cumprod, timesteps[:total_steps])).to(x.device)
+        apg_tab = None if apg is None else torch.from_numpy(apg_coef_table(self.alphas_cumprod, timesteps[:total_steps], *apg)).to(x.device)
+        per_sample = x.numel() // x.shape[0]
         reps = replica_count(guided, pag is not None)
         table = self._coef_table(total_steps, scale, x.device)
         rng_tab = self._rng_table(total_steps, x.device)
@@ -801,6 +880,8 @@ class DDIMSampler(object):
                             None if mode is None else (st["deep"], mode), st.get("window"), None if pag is None else pag[1],
                             None if sag is None else st["sag"]["mass"])
             eps = eps.contiguous()
+            if apg is not None:     # replica 0 rewritten from the latent, the pair and the running direction
+                ops.apg_fold(st["xs"], eps, st["apg_v"], st["apg_coef"], per_sample, out_fac=st["apg_fac"])
             if pag is not None:
                 eps = ops.pag_fold(eps, reps, st["pag_w"])      # the folded pair (single): what every update below reads
             if sag is not None:     # degrade, second forward, fold into replica 0: what every update below reads
@@ -820,12 +901,16 @@ class DDIMSampler(object):
         intermediates = {"pred_xt": [], "pred_x0": []}
         if rescale > 0.:
             intermediates["guidance_rescale"] = []
+        if apg is not None:
+            intermediates["apg"] = []
         for i in range(total_steps):
             index = total_steps - i - 1
             st["ts"].copy_(steps_dev[i].expand(st["ts"].shape[0]))       # device-side refresh, no host sync
             st["coef"].copy_(table[index])
             if sag_tab is not None:
                 st["sag"]["coef"].copy_(sag_tab[index])
+            if apg_tab is not None:
+                st["apg_coef"].copy_(apg_tab[index])
             if rng_tab is not None:
                 st["rng"].copy_(rng_tab[i])
             if inpaint is not None:
@@ -848,6 +933,8 @@ class DDIMSampler(object):
                 intermediates["pred_x0"].append(st["p0"].to(dtype).clone())
                 if rescale > 0.:
                     intermediates["guidance_rescale"].append(st["kfac"].clone())
+                if apg is not None:
+                    intermediates["apg"].append(st["apg_fac"].clone())
         torch.cuda.set_rng_state(rng_after, x.device)
         return st["xs"].clone(), intermediates
 
@@ -907,11 +994,13 @@ class DDIMSampler(object):
             return None
 
     def _step(self, x, x_info, c_info_list, step, index, guided, scale, temperature, single, noise_dropout=0., rescale=None,
-              deep=None, window=None, pag=None, sag=None):
+              deep=None, window=None, pag=None, sag=None, apg=None):
         """One p_sample_ddim (reference ddim.py:129-171 / 244-298) on the fp16 device latent `x` [B,C,H,W]: (x_prev, pred_x0,
         the guidance-rescale factors [B] or None).  rescale: None, or the device scalars of _rescale_scalars.  deep, window: _eps's.
         pag: None, or (layers, the fold's weight as a device fp32 [1]) of perturbed-attention guidance.
-        sag: None, or the state of _sag_eager: the step of self-attention guidance (_sag_fold) between the forward and the update."""
+        sag: None, or the state of _sag_eager: the step of self-attention guidance (_sag_fold) between the forward and the update.
+        apg: None, or (running direction fp32 like x, the step's device row of apg_coef_table, fac fp32 [B, 4] to write) of adaptive
+        projected guidance: ops.apg_fold right behind the forward, as in the static loop."""
         reps = replica_count(guided, pag is not None)
         rows = reps * x.shape[0] * (1 if window is None else window["plan"]["m"])
         t_in = torch.full((rows,), step, device=x.device, dtype=torch.long)
@@ -933,6 +1022,8 @@ class DDIMSampler(object):
                        a_prev=float(self.ddim_alphas_prev[index]), sigma=sigma,
                        sqrt_one_minus_at=float(self.ddim_sqrt_one_minus_alphas[index]), noise=noise)
         eps = eps.contiguous()
+        if apg is not None:
+            ops.apg_fold(x, eps, apg[0], apg[1], x.numel() // x.shape[0], out_fac=apg[2])
         if pag is not None:
             eps = ops.pag_fold(eps, reps, pag[1])
         if sag is not None:
@@ -977,7 +1068,10 @@ class DDIMSampler(object):
         _hypertile_arg(x_info, self.model, x_info["x"].shape)   # and HyperTile: the step's forward applies it (_eps)
         sag = _sag_arg(x_info, self.model, x_info["x"].shape)   # and self-attention guidance: the step runs its second forward
         assert not use_original_steps and not repeat_noise
+        apg = _apg_arg(x_info)      # adaptive projected guidance keeps a running direction between the steps of a loop
         cis, guided, scale, phi = self._cfg_contexts(c_info_list, pag=pag is not None)
+        if apg is not None and guided:
+            raise ValueError("apg: adaptive projected guidance runs whole sample() loops; p_sample_ddim* keeps no direction between steps")
         x = x_info["x"]
         if pag is not None:
             pag = (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)), device=x.device, dtype=torch.float32))

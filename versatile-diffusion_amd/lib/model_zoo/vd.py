@@ -713,6 +713,39 @@ def _sag_arg(x_info, model, shape=None):
     return float(value), float(sigma)
 
 
+# ---- adaptive projected guidance (x_info['apg_eta'], ['apg_norm_threshold'], ['apg_momentum']) -----------------------------------
+# Sadat, Hilliges, Weber, "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion Models" (2024); diffusers'
+# AdaptiveProjectedGuidance.  Nothing in the forward: the samplers fold it into the step's prediction (ddim.apg_guided_eps).
+APG_NEUTRAL = (1.0, 0.0, 0.0)       # eta, norm threshold, momentum: plain classifier-free guidance
+
+
+def _apg_arg(x_info):
+    """The sampler keys of adaptive projected guidance validated: None when none of x_info['apg_eta'] (default 1),
+    ['apg_norm_threshold'] (default 0 = no clipping) and ['apg_momentum'] (default 0) is present (a key that is None counts as
+    absent) or when the triple is the neutral (1, 0, 0) (off: today's call), else (eta, r, beta) as floats.  ValueError (matching
+    'apg') for an eta that is no real number in [0, 1], a threshold that is no finite real number >= 0, a momentum that is no finite
+    real number with |beta| < 1 (a bool or a string is no real number), and for the combination left out of scope on purpose:
+    sag_scale, whose fold reads replica 0 as the first forward's e_u, which this fold has rewritten.  Touches no device."""
+    raw = [x_info.get(k) for k in ("apg_eta", "apg_norm_threshold", "apg_momentum")]
+    if all(v is None for v in raw):
+        return None
+    real = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(float(v))
+    eta, r, beta = [d if v is None else v for v, d in zip(raw, APG_NEUTRAL)]
+    if not real(eta) or not 0. <= float(eta) <= 1.:
+        raise ValueError("x_info['apg_eta'] must be a real number in [0, 1], got %r" % (eta,))
+    if not real(r) or float(r) < 0.:
+        raise ValueError("x_info['apg_norm_threshold'] must be a finite real number >= 0, got %r" % (r,))
+    if not real(beta) or not abs(float(beta)) < 1.:
+        raise ValueError("x_info['apg_momentum'] must be a finite real number with |beta| < 1, got %r" % (beta,))
+    out = (float(eta), float(r), float(beta))
+    if out == APG_NEUTRAL:
+        return None
+    if x_info.get("sag_scale") not in (None, 0, 0.):
+        raise ValueError("apg with sag_scale is out of scope on purpose: the fold of self-attention guidance reads replica 0 as the "
+                         "first forward's e_u, which the apg fold has rewritten")
+    return out
+
+
 def _sag_fwd_arg(x_info, contexts):
     """x_info['sag'] (extension key of apply_model*, set by the samplers) validated: None, or the caller-owned fp32 [T, B, Nm] device
     tensor -- T the number of context types of the call, B the samples of ONE replica, Nm the tokens of the middle context block."""

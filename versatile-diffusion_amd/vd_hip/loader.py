@@ -129,6 +129,7 @@ PROTOTYPES = {
     "vd_sag_mass_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _F, _P]),
     "vd_sag_degrade_f16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vd_sag_fold_f16": (_I, [_P, _P, _L, _P, _P]),
+    "vd_apg_fold_f16": (_I, [_P, _P, _P, _P, _P, _L, _L, _P]),
     "vd_tome_match_f16": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
     "vd_tome_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "vd_tome_merge_f16": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _I, _P, _I, _L, _P]),

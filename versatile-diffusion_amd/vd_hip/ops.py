@@ -1508,6 +1508,33 @@ def pag_fold(eps, reps, w):
     return eps[:(reps - 1) * (eps.shape[0] // reps)]
 
 
+def apg_fold(x, eps, v, coef, per_sample, out_fac=None):
+    """The fold of an adaptive-projected-guidance step (vd_apg_fold_f16, contract in include/vd_hip.h): x fp16 [B, ...] (the
+    latent, n elements), eps fp16 whose leading 2 n elements are [e_uncond ; e_cond] (further replicas may follow), v fp32 with n
+    elements (the running direction: read when coef[3] != 0, always written), coef a device fp32 [8] row of
+    ddim.apg_coef_table, per_sample the elements of one sample.  Rewrites replica 0 of eps in place, one launch.  Returns
+    (eps, fac): fac fp32 [n / per_sample, 4] = {||v||, k, p, ||D_c||} per sample (`out_fac` if given)."""
+    _req(x, "x"); _req(eps, "eps"); _req(v, "v", torch.float32); _req(coef, "coef", torch.float32)
+    per_sample = int(per_sample)
+    n = x.numel()
+    if n == 0 or eps.numel() < 2 * n:
+        raise VdHipError("apg_fold: eps has %d elements, expected at least [e_uncond ; e_cond] of x's %d" % (eps.numel(), n))
+    if per_sample <= 0 or n % per_sample:
+        raise VdHipError("apg_fold: x holds %d elements, not a multiple of per_sample = %d" % (n, per_sample))
+    if v.numel() != n:
+        raise VdHipError("apg_fold: v has %d elements, expected %d" % (v.numel(), n))
+    if coef.numel() < 8:
+        raise VdHipError("apg_fold: coef must hold 8 elements, got %d" % coef.numel())
+    if out_fac is None:
+        out_fac = torch.empty((n // per_sample, 4), dtype=torch.float32, device=x.device)
+    _req(out_fac, "out_fac", torch.float32)
+    if out_fac.numel() != 4 * (n // per_sample):
+        raise VdHipError("apg_fold: out_fac has %d elements, expected %d" % (out_fac.numel(), 4 * (n // per_sample)))
+    with _Timed("apg_fold_kernel", 20.0 * n, 2.0 * n * 6 + 4.0 * n * 3):
+        _check(lib().vd_apg_fold_f16(_ptr(x), _ptr(eps), _ptr(v), _ptr(coef), _ptr(out_fac), n, per_sample, _stream()))
+    return eps, out_fac
+
+
 SAG_MAX_TOKENS = 1024      # vd_sag_mass_f16 keeps the row statistics of one head in LDS
 
 
@@ -1939,7 +1966,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "tile_tokens", "untile_tokens", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "apg_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "tile_tokens", "untile_tokens", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
