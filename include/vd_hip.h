@@ -810,6 +810,35 @@ int vd_sag_fold_f16(void* eps, const void* e_d, int64_t n, const float* w, hipSt
 int vd_apg_fold_f16(const void* x, void* eps, float* v, const float* coef, float* fac, int64_t n, int64_t per_sample,
                     hipStream_t stream);
 
+/* LoRA adapters (Hu et al., "LoRA: Low-Rank Adaptation of Large Language Models", 2021; not in the reference): the merge of up to
+ * eight rank-r updates into one weight matrix, W = base + sum_a scale_a up_a down_a.  One entry point (additive to ABI 8), one launch
+ * per parameter, between forwards (lib/model_zoo/lora.py).  The merge is always recomputed from a kept base, in a fixed order, so
+ * its bits do not depend on which adapters were active before, and switching every adapter off gives the base back.
+ *
+ * vd_lora_merge: base and out are [N][K] row-major in the parameter's dtype, fp32 (out_is_f16 == 0) or fp16 (out_is_f16 != 0), and
+ * never alias; terms is a HOST array of n_terms entries (copied into the kernel arguments: the array may be freed on return), up is
+ * DEVICE fp32 [N][r] row-major, down DEVICE fp32 [r][K] row-major, scale the adapter's strength times alpha / r, formed by the host
+ * in double and rounded once.  Per element, each line ONE fp32 operation, in this order and no other:
+ *     acc = (float)base[n][k]                               exact
+ *     for each term a in table order:
+ *         d = 0;  for j = 0 .. r_a - 1 ascending:  d = fmaf(up_a[n][j], down_a[j][k], d)
+ *         acc = fmaf(scale_a, d, acc)
+ *     out[n][k] = acc                                       as it is (fp32), or rounded once to fp16, to nearest even
+ * VALU fp32 throughout (the summation order inside an MFMA is not part of any contract), compiled without contraction; no padded
+ * rank step is executed.  An element's result is a pure function of its own operands: the same bits for any alignment (16-byte /
+ * 8-byte accesses of base and out when K % 4 == 0 and both are 16-byte aligned, else element-wise accesses of the same elements),
+ * tile position or device.  Any N, K >= 1, 1 <= r <= 256, 1 <= n_terms <= 8.  Neither allocates nor synchronises (capturable).
+ * Returns < 0 (vd_last_error, the text starts with this entry's name) for null pointers (the terms' included), n_terms outside 1..8,
+ * r outside 1..256, N or K <= 0, base == out or overlapping, or operands not aligned to their element size. */
+typedef struct VdLoraTerm {
+    const float* up;   /* [N][r] row-major */
+    const float* down; /* [r][K] row-major */
+    float scale;
+    int r;
+} VdLoraTerm;
+int vd_lora_merge(const void* base, void* out, int out_is_f16, const VdLoraTerm* terms, int n_terms, int N, int K,
+                  hipStream_t stream);
+
 /* Token merging for self-attention (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion", 2023; the tomesd package with
  * sx = sy = 2, use_rand = False; not in the reference).  Four entry points (additive to ABI 8); none allocates or synchronises
  * (capturable).  Every one returns < 0 (vd_last_error, the text starts with the entry's name) for null pointers, an empty problem,

@@ -47,6 +47,10 @@ class VdFfChain(ctypes.Structure):
                 ("period_rows", ctypes.c_int32)]
 
 
+class VdLoraTerm(ctypes.Structure):
+    _fields_ = [("up", ctypes.c_void_p), ("down", ctypes.c_void_p), ("scale", ctypes.c_float), ("r", ctypes.c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/vd_hip.h one to one (checked by
 # tests/test_host_cpu.py::test_capi_exports_every_declared_symbol)
 _P, _I, _F, _L, _Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_size_t
@@ -130,6 +134,7 @@ PROTOTYPES = {
     "vd_sag_degrade_f16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vd_sag_fold_f16": (_I, [_P, _P, _L, _P, _P]),
     "vd_apg_fold_f16": (_I, [_P, _P, _P, _P, _P, _L, _L, _P]),
+    "vd_lora_merge": (_I, [_P, _P, _I, ctypes.POINTER(VdLoraTerm), _I, _I, _I, _P]),
     "vd_tome_match_f16": (_I, [_P, _I, _L, _I, _I, _I, _I, _P, _P, _P]),
     "vd_tome_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "vd_tome_merge_f16": (_I, [_P, _I, _L, _I, _P, _I, _I, _I, _I, _P, _I, _L, _P]),

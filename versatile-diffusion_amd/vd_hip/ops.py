@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-from .loader import VdFfChain, VdGemmDesc, VdHipError, lib
+from .loader import VdFfChain, VdGemmDesc, VdHipError, VdLoraTerm, lib
 
 EPI_BIAS, EPI_ROWVEC, EPI_RESIDUAL, EPI_BIAS_ALONG_M, EPI_OUT_F32, EPI_LNFOLD, EPI_LN_INLOOP = 1, 2, 4, 8, 16, 32, 64
 EPI_GROUPNORM, EPI_GN_SILU, EPI_LN_SUMS = 128, 256, 512
@@ -1535,6 +1535,58 @@ def apg_fold(x, eps, v, coef, per_sample, out_fac=None):
     return eps, out_fac
 
 
+LORA_MAX_TERMS, LORA_MAX_RANK = 8, 256      # vd_lora_merge
+
+
+def lora_merge(base, terms, out=None):
+    """base + sum_a scale_a up_a down_a with written-out roundings (vd_lora_merge, contract in include/vd_hip.h): base [N, K] fp32
+    or fp16 (a weight viewed as a matrix), terms a list of 1..8 (up fp32 [N, r], down fp32 [r, K], scale float) with 1 <= r <= 256,
+    merged in list order.  Writes `out` (same shape, dtype and device as base, never base itself and never an nn.Parameter: the
+    kernel's store does not advance a tensor's version, so a parameter is updated by the caller with param.copy_(out)); allocated
+    when None.  One launch.  Returns out.  ValueError for wrong dtypes, shapes, devices or non-contiguous operands."""
+    def bad(msg):
+        raise ValueError("lora_merge: " + msg)
+    if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.numel() == 0:
+        bad("base must be a non-empty [N, K] tensor")
+    if base.dtype not in (torch.float32, torch.float16):
+        bad("base must be float32 or float16, got %s" % base.dtype)
+    if not base.is_contiguous():
+        bad("base must be contiguous")
+    if not base.is_cuda:
+        raise VdHipError("lora_merge: base must live on the GPU (no CPU fallback in the product path)")
+    N, K = base.shape
+    terms = list(terms)
+    if not 1 <= len(terms) <= LORA_MAX_TERMS:
+        bad("%d terms, expected 1..%d" % (len(terms), LORA_MAX_TERMS))
+    table = (VdLoraTerm * len(terms))()
+    for a, (up, down, scale) in enumerate(terms):
+        for t, name in ((up, "up"), (down, "down")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+                bad("%s of term %d must be a 2-d float32 tensor" % (name, a))
+            if t.device != base.device:
+                bad("%s of term %d lives on %s, base on %s" % (name, a, t.device, base.device))
+            if not t.is_contiguous():
+                bad("%s of term %d must be contiguous" % (name, a))
+        r = up.shape[1]
+        if not 1 <= r <= LORA_MAX_RANK:
+            bad("rank %d of term %d outside 1..%d" % (r, a, LORA_MAX_RANK))
+        if tuple(up.shape) != (N, r) or tuple(down.shape) != (r, K):
+            bad("term %d has up %s and down %s, expected [%d, r] and [r, %d]" % (a, tuple(up.shape), tuple(down.shape), N, K))
+        table[a] = VdLoraTerm(up.data_ptr(), down.data_ptr(), float(scale), r)
+    if out is None:
+        out = torch.empty_like(base)
+    if not isinstance(out, torch.Tensor) or isinstance(out, torch.nn.Parameter) or out.requires_grad:
+        bad("out must be a plain tensor (update a parameter with param.copy_(out))")
+    if out.dtype != base.dtype or tuple(out.shape) != (N, K) or out.device != base.device or not out.is_contiguous():
+        bad("out must be contiguous with base's shape, dtype and device")
+    if out.data_ptr() == base.data_ptr():
+        bad("out must not alias base")
+    flops = 2.0 * N * K * sum(t[0].shape[1] + 1 for t in terms)
+    with _Timed("lora_merge_kernel", flops, 2.0 * N * K * base.element_size()):
+        _check(lib().vd_lora_merge(_ptr(base), _ptr(out), int(base.dtype == torch.float16), table, len(terms), N, K, _stream()))
+    return out
+
+
 SAG_MAX_TOKENS = 1024      # vd_sag_mass_f16 keeps the row statistics of one head in LDS
 
 
@@ -1966,7 +2018,7 @@ def _guarded(fn):
 
 for _name in ("gemm", "gemm_row320", "row320_chain", "groupnorm_affine", "ff_geglu", "xattn", "row_stats", "linear", "conv2d_nhwc", "groupnorm_silu", "groupnorm0d_silu", "layernorm", "attention", "softmax_rows", "softmax_rows_f32",
               "timestep_embedding", "cfg_ddim_step", "cfg_ddim_step_dev", "cfg_dpmpp_step_dev", "cfg_dpmpp_sde_step_dev", "cfg_rescale_factor", "cfg_ddim_step_rs", "cfg_ddim_step_dev_rs",
-              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "apg_fold", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "tile_tokens", "untile_tokens", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
+              "cfg_dpmpp_step_dev_rs", "cfg_dpmpp_sde_step_dev_rs", "cfg_unipc_step_dev", "cfg_unipc_step_dev_rs", "philox_normal", "masked_blend", "window_gather", "window_merge", "window_merge_masked", "tile_blend", "freeu", "pag_fold", "apg_fold", "lora_merge", "tome_match", "tome_plan", "tome_merge", "tome_unmerge", "tile_tokens", "untile_tokens", "q_sample", "nchw_to_nhwc", "nhwc_to_nchw",
               "im2col_small", "diag_gaussian_sample", "axpby", "embed_tokens", "clip_vision_embed", "patchify",
               "unary", "scale_by_row_norm_", "image_to_u8", "clip_preprocess", "probe_lds_tr16", "mask_patch_weights", "color_adjust", "adjust_rank"):
     globals()[_name] = _guarded(globals()[_name])
