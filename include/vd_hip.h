@@ -730,6 +730,43 @@ int vd_attention_ident_f16(const void* q, const void* k, const void* v, void* ou
  * for a null pointer, n <= 0, reps outside {2, 3} or a misaligned eps / w.  Neither allocates nor synchronises (capturable). */
 int vd_pag_fold_f16(void* eps, int64_t n, int reps, const float* w, hipStream_t stream);
 
+/* Smoothed energy guidance (Hong, "Smoothed Energy Guidance: Guiding Diffusion Models with Reduced Energy Curvature of Attention",
+ * NeurIPS 2024; ComfyUI's SEG node, diffusers' SmoothedEnergyGuidance; not in the reference).  The perturbed replica of
+ * perturbed-attention guidance with a milder perturbation: chosen self-attention layers keep their softmax and Gaussian-blur the
+ * replica's QUERIES over the token grid, per channel; k and v are untouched.  The prediction is combined by vd_pag_fold_f16 as
+ * above, e = e_u + s (e_c - e_u) + s_seg (e_c - e_p).  One entry point (additive to ABI 8).
+ *
+ * vd_attention_qblur_f16: the arguments of vd_attention_f16 plus blur_from, the token grid gh x gw (gh * gw == Nq == Nk), the taps
+ * (DEVICE fp32 [2 R + 1], w[d] at index d + R; one captured call serves every sigma of the same R), R, and the caller's workspace qb,
+ * fp16 [(B - blur_from)][Nq][H * D] contiguous.  Samples b < blur_from: exactly the call vd_attention_f16(q, k, v, out, blur_from,
+ * ...) -- the same kernel instances, so their bits are those of a call on these samples alone.  Samples b >= blur_from: ONE launch
+ * writes their blurred queries qb from the strided q (which may be a column slice of a fused [B, N, 3 C] projection, ld = 3 C), then
+ * ONE call vd_attention_f16(qb, k + blur_from * sk, v + blur_from * sv, out + blur_from * so, B - blur_from, ..., ldq = H * D,
+ * sq = Nq * H * D, ...) -- so their output is, bit for bit, that call on qb.  blur_from == B launches no blur and does not touch qb
+ * (which may then be NULL); blur_from == 0 runs one softmax call.  With token n = y * gw + x and channel c, per element:
+ * R >= 0 (the taps are whatever the caller loads; lib/model_zoo/vd.py's seg_taps forms the normalised Gaussian in double and rounds
+ * once), each line ONE fp32 operation:
+ *     h[y'][x] = 0;  for dx = -R .. R ascending:  h = fmaf(w[dx], fp32(q[refl(x + dx, gw) of row y']), h)      the horizontal pass
+ *     a        = 0;  for dy = -R .. R ascending:  a = fmaf(w[dy], h[refl(y + dy, gh)][x], a)                    the vertical pass
+ *     qb[n][c] = fp16(a)         a rounding of its own, to nearest even; h is kept in fp32 and never rounded to fp16
+ * refl(i, n) is the reflection that does not repeat the edge (torch's 'reflect' padding), folded as often as needed, period
+ * 2 (n - 1): i mod 2 (n - 1) = j, then j if j < n else 2 (n - 1) - j; 0 for n == 1.  So any R is defined, R >= n too, and for R < n the
+ * result is that of F.pad(mode="reflect") followed by a depthwise conv2d with the outer product of the taps.
+ * R == -1 (sigma = infinity, the upstream default): every query of a sample becomes its mean query.  Per (sample, channel): thread t
+ * of 256 adds the tokens t, t + 256, ... ascending in fp32 from 0, the 256 partial sums are added in a fixed binary tree (t takes
+ * t + 128, then t + 64, ... t + 1), one IEEE fp32 division by (float)Nq, one rounding to fp16, to nearest even, broadcast to all Nq
+ * rows.  The order depends on Nq alone: no atomics, the same bits run to run, for any batch, grid of the launch or graph.
+ * An element of qb is a pure function of its sample's q, the taps and the grid: whether the horizontal pass is staged in LDS (a band
+ * of grid rows per block) or recomputed per vertical tap in registers (a hull that does not fit) the operations above are the same.
+ * Returns < 0 (vd_last_error, the text starts with this entry's name) for null pointers, an empty problem, Nq != Nk, causal != 0,
+ * blur_from outside [0, B], gh * gw != Nq, R < -1, R >= 0 without taps or with taps not 4-byte aligned, H * D, ldq or sq no multiple
+ * of 8, ldq below H * D, q or qb not 16-byte aligned, and whatever vd_attention_f16 refuses (its text follows the name).  Neither
+ * allocates nor synchronises (capturable). */
+int vd_attention_qblur_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int Nq, int Nk, int D,
+                           int ldq, int ldk, int ldv, int ldo, int64_t sq, int64_t sk, int64_t sv, int64_t so,
+                           float scale, int causal, int blur_from, int gh, int gw, const float* taps, int R, void* qb,
+                           hipStream_t stream);
+
 /* Self-attention guidance (Hong et al., "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance", ICCV 2023;
  * diffusers' StableDiffusionSAGPipeline(sag_scale); not in the reference).  A step reads the self-attention map of the middle
  * context block, blurs the pixels of its data prediction that the map attends to, re-noises the result, predicts a second time

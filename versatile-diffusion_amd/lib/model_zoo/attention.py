@@ -144,7 +144,7 @@ class CrossAttention(nn.Module, PackCache):
                             lambda: fold_layernorm(_h(self.to_q.weight), None, ln))
 
     def forward(self, x, context=None, res=None, kv=None, ln=None, qkv=None, ln_sums=None, out_sums=None, defer_out=False, repeat=1,
-                ident_from=None, tome=None, sag=None, tile=None):
+                ident_from=None, tome=None, sag=None, tile=None, blur_from=None, blur=None):
         """ln_sums: row statistics of x for `ln` (from x's producer); out_sums: zeroed fp32 [rows, 2] the output projection
         accumulates the row statistics of ITS output into (for the LayerNorm in front of the next block part).
         defer_out: return the attention output `a` WITHOUT the output projection (the caller folds to_out + res into its next
@@ -168,8 +168,18 @@ class CrossAttention(nn.Module, PackCache):
         cut into th x tw tiles and every tile attends inside itself: q | k | v as always, whoever computed it -> ops.tile_tokens of
         the fused tensor -> ops.attention on its [B nt, th tw, *] slices (nt = (H / th) (W / tw)) -> ops.untile_tokens -> to_out.
         It does not combine with tome or sag.  With ident_from the identity rows are per token and commute with the permutation:
-        the tiled batch takes ident_from * nt, so the perturbed samples are v, bit for bit, as without tiles."""
+        the tiled batch takes ident_from * nt, so the perturbed samples are v, bit for bit, as without tiles.
+        blur_from, blur (self-attention only; smoothed energy guidance, contract in include/vd_hip.h): None, or an index and
+        (taps, R, gh, gw[, qb]) -- the samples from blur_from on attend with their projected queries blurred over the gh x gw token
+        grid (ops.attention(blur_from=..., blur=..., qb=...)), whoever computed qkv; k and v are untouched.  It does not combine
+        with ident_from, tome or tile."""
         c = self.inner
+        if (blur_from is None) != (blur is None):
+            raise ops.VdHipError("CrossAttention(blur_from=%r, blur=%r): the index and the blur setting go together" % (blur_from, blur))
+        if blur_from is not None and not (context is None and kv is None):
+            raise ops.VdHipError("CrossAttention(blur_from=%r): the query blur applies to self-attention only" % (blur_from,))
+        if blur_from is not None and (ident_from is not None or tome is not None or tile is not None):
+            raise ops.VdHipError("CrossAttention(blur_from=%r): the query blur does not combine with ident_from, tome or tile" % (blur_from,))
         if tile is not None and not (context is None and kv is None):
             raise ops.VdHipError("CrossAttention(tile=...): tiled attention applies to self-attention only")
         if tile is not None and (tome is not None or sag is not None):
@@ -224,6 +234,9 @@ class CrossAttention(nn.Module, PackCache):
                 m = ops.tome_merge(qkv, row_of, tH, tW, r)
                 a = ops.attention(m[..., :c], m[..., c:2 * c], m[..., 2 * c:], self.heads, scale=self.scale)
                 a = ops.tome_unmerge(a, row_of, tH, tW, r)
+            elif blur_from is not None:
+                a = ops.attention(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, scale=self.scale,
+                                  blur_from=int(blur_from), blur=tuple(blur[:4]), qb=blur[4] if len(blur) > 4 else None)
             elif ident_from is None:
                 a = ops.attention(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, scale=self.scale)
             else:
@@ -270,7 +283,7 @@ class BasicTransformerBlock(nn.Module):
         self.checkpoint = checkpoint  # kept for config compatibility; inference never re-computes
 
     def forward(self, x, context=None, kv=None, qkv=None, ln1_sums=None, post=None, sync=None, repeat=1, ff_post=None, ident_from=None,
-                tome=None, sag=None, tile=None):
+                tome=None, sag=None, tile=None, blur_from=None, blur=None):
         """post = (wp [C, C], bp, alpha, res [B, N, C], stat_img_rows): SpatialTransformer.proj_out (+ skip / context mixing) to be
         folded into the block's last launch.  Returns (tensor, True) when it was -- the tensor is then proj_out's output -- else
         the block output (the caller runs proj_out).  sync: called right before a launch that reads post's `res` (see
@@ -287,15 +300,19 @@ class BasicTransformerBlock(nn.Module):
         input.  With repeat > 1 the merge runs on the one replica attn1 sees.
         sag: handed to attn1 (CrossAttention.forward): the buffer that receives the column mass of its leading samples.
         tile: handed to attn1 (CrossAttention.forward): (H, W, th, tw) of HyperTile.  With repeat > 1 the tiled attention runs on
-        the one replica attn1 sees."""
+        the one replica attn1 sees.
+        blur_from, blur: handed to attn1 (CrossAttention.forward); like ident_from they need repeat == 1."""
         if tome is not None:
             tome = (tome[0], tome[1], tome[2], x, tome[3] if len(tome) > 3 else None)
+        if blur_from is not None and repeat > 1:
+            raise ops.VdHipError("BasicTransformerBlock(repeat=%d, blur_from=%r): a perturbed replica cannot share attn1" % (repeat, blur_from))
+        bkw = {} if blur_from is None else {"blur_from": blur_from, "blur": blur}
         if ident_from is not None and repeat > 1:
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d, ident_from=%r): a perturbed replica cannot share attn1" % (repeat, ident_from))
         if repeat > 1 and not period_consumers(x.shape[-1], self.attn2.heads):
             raise ops.VdHipError("BasicTransformerBlock(repeat=%d): width %d has no consumers with a batch period" % (repeat, x.shape[-1]))
         if hip_layers.LN_FOLD:  # the three LayerNorms ride in the q/k/v, q and GEGLU projections (VD_EPI_LNFOLD)
-            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome, sag=sag, tile=tile)
+            x = self.attn1(x, res=x, ln=self.norm1, qkv=qkv, ln_sums=ln1_sums, ident_from=ident_from, tome=tome, sag=sag, tile=tile, **bkw)
             C = x.shape[-1]
             fops = self.ff.chain_operands(self.norm3) if (x.is_contiguous() and ops.ff_geglu_supported(C)) else None
             if fops is not None and (ops.ff_chain_supported(C, "pre") or (post is not None and ops.ff_chain_supported(C, "post"))):
@@ -337,7 +354,7 @@ class BasicTransformerBlock(nn.Module):
             s3 = None if ops.ff_geglu_supported(C) else ops.rowsum_take(x.numel() // C, x.device)
             x = self.attn2(x, context=context, res=x, kv=kv, ln=self.norm2, out_sums=s3)
             return self.ff(x, res=x, ln=self.norm3, ln_sums=getattr(x, "_vd_rowsums", None), post=ff_post, sync=sync)
-        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome, sag=sag, tile=tile)
+        x = self.attn1(self.norm1(x), res=x, ident_from=ident_from, tome=tome, sag=sag, tile=tile, **bkw)
         x = self.attn2(self.norm2(x), context=context, res=x, kv=kv)
         x = self.ff(self.norm3(x), res=x)
         return x
@@ -369,7 +386,8 @@ class SpatialTransformer(nn.Module):
         and of the chained tail (vd.run_unet hands a guided batch over un-replicated only then)."""
         return period_consumers(self.proj_in.out_channels, self.transformer_blocks[0].attn2.heads)
 
-    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None):
+    def forward(self, x, context=None, kv=None, alpha=1.0, res=None, sync=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None,
+                blur_from=None, blur=None):
         """Returns alpha * (proj_out(...) + bias) + res, res defaulting to x (the block's own skip).
         alpha/res implement VD's context mixing sum_i r_i * ST_i(x) without extra passes.
         sync: callable invoked right before the ONE launch that reads `res` (the last of the block): the caller runs the blocks
@@ -384,7 +402,14 @@ class SpatialTransformer(nn.Module):
         sag: None, or a contiguous fp32 [n, H W] view, n <= B: the block's self-attention writes the column mass of its attention map
         for the samples [0, n) into it (self-attention guidance); the block's output is untouched.
         tile: None, or (th, tw) of HyperTile: this block's self-attention runs inside th x tw tiles of its H x W grid
-        (CrossAttention.forward(tile=(H, W, th, tw))), under repeat > 1 too: once per guidance pair."""
+        (CrossAttention.forward(tile=(H, W, th, tw))), under repeat > 1 too: once per guidance pair.
+        blur_from, blur = (taps, R[, qb]) (smoothed energy guidance, needs repeat == 1): samples [blur_from, B) of x attend in this
+        block's self-attention with their queries blurred over its H x W grid (CrossAttention.forward(blur=(taps, R, H, W[, qb]))),
+        whether q | k | v come from the chained entry kernel (width 320) or from the block's own projection."""
+        assert repeat == 1 or blur_from is None, "a perturbed replica takes the replicated input"
+        bkw = {}
+        if blur_from is not None:
+            bkw = {"blur_from": int(blur_from), "blur": (blur[0], int(blur[1]), x.shape[1], x.shape[2]) + tuple(blur[2:])}
         if tile is not None:
             tile = (x.shape[1], x.shape[2], int(tile[0]), int(tile[1]))
         if tome is not None:
@@ -411,7 +436,7 @@ class SpatialTransformer(nn.Module):
                 wp, bp = self.proj_out._w()
                 post = (wp, bp, float(alpha), pres.view(B, H * W, C), H * W)
             h = blk(h, context=context, kv=kv, qkv=qkv, post=post, sync=sync, repeat=repeat, ident_from=ident_from, tome=tome, sag=sag,
-                    tile=tile)
+                    tile=tile, **bkw)
             if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the block's last launch
                 out = h[0]
                 st = ops.stats_of(out)
@@ -434,7 +459,7 @@ class SpatialTransformer(nn.Module):
                 ff_post = (self.proj_out, float(alpha), pres, H * W)
         h = self.transformer_blocks[0](h.view(B, H * W, -1), context=context, kv=kv, ln1_sums=getattr(h, "_vd_rowsums", None),
                                        repeat=repeat, ff_post=ff_post, sync=sync if ff_post is not None else None, ident_from=ident_from,
-                                       tome=tome, sag=sag, tile=tile)
+                                       tome=tome, sag=sag, tile=tile, **bkw)
         if isinstance(h, tuple):   # proj_out (+ skip, alpha, statistics) ran inside the feed-forward's output GEMM
             out = h[0]
             st = ops.stats_of(out)

@@ -21,8 +21,8 @@ from vd_hip import ops
 
 from . import windows
 from .diffusion_utils import make_ddim_sampling_parameters, make_ddim_timesteps
-from .vd import (DeepCache, _apg_arg, _freeu_arg, _hypertile_arg, _pag_arg, _sag_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
-                 kv_rows, hypertile_blocks, sag_map_size, sag_taps, tome_blocks)
+from .vd import (DeepCache, _apg_arg, _freeu_arg, _hypertile_arg, _pag_arg, _sag_arg, _seg_arg, _tome_arg, capture_stream, deep_cut, kv_mark_stale, kv_refresh, kv_refreshable,
+                 kv_rows, hypertile_blocks, sag_map_size, sag_taps, seg_taps, seg_workspace_elems, tome_blocks)
 
 
 def inpaint_blend_table(alphas_cumprod, timesteps):
@@ -397,6 +397,12 @@ class DDIMSampler(object):
             raise ValueError("cache_interval > 1 does not combine with window: DeepCache would keep one feature per chunk of windows")
         # x_info['pag_scale'] / ['pag_layers'] (extension keys, vd._pag_arg): None, or (s_pag, layers); raises like the others
         pag = _pag_arg(x_info, self.model)
+        # x_info['seg_scale'] / ['seg_blur_sigma'] / ['seg_layers'] (extension keys, vd._seg_arg): None, or (s_seg, layers, sigma);
+        # raises like the others.  Smoothed energy guidance IS the perturbed replica of pag with another perturbation (and never in
+        # the same call), so from here on `pag` is whichever is on: (scale, layers) or (scale, layers, sigma)
+        seg = _seg_arg(x_info, self.model, shape)
+        if seg is not None:
+            pag = seg
         # x_info['tome_ratio'] / ['tome_max_downsample'] (extension keys, vd._tome_arg): None, or the TokenMerge; raises like the
         # others.  The setting travels with every forward (_eps), like FreeU's
         tome = _tome_arg(x_info, self.model, shape)
@@ -444,8 +450,9 @@ class DDIMSampler(object):
                 intermediates["apg"] = []
             deep = DeepCache(depth) if interval > 1 else None
             wstate = None if window is None else self._window_state(window, x, guided, pag is not None)      # once per call
-            pag_step = None if pag is None else (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)),
-                                                                    device=x.device, dtype=torch.float32))
+            pag_step = None if pag is None else (self._pert_fwd(pag, x.device),
+                                                 torch.full((1,), float(pag_weight(scale, pag[0], guided)),
+                                                            device=x.device, dtype=torch.float32))
             sag_step = None if sag is None else self._sag_eager(sag, scale, guided, c_info_list, x)
             if phi > 0.:
                 intermediates["guidance_rescale"] = []
@@ -471,7 +478,7 @@ class DDIMSampler(object):
         if interval > 1:
             intermediates["cache_full_steps"] = list(range(0, total_steps, interval))
         if pag is not None:
-            intermediates["pag_layers"] = pag[1]
+            intermediates["pag_layers" if seg is None else "seg_layers"] = pag[1]
         if sag is not None:
             intermediates["sag_map"] = sag_map_size(self.model.diffuser[x_info["type"]], x.shape[2], x.shape[3])
         if tome is not None:
@@ -593,6 +600,8 @@ class DDIMSampler(object):
         x_info['freeu'] (FreeU, vd.freeu_setting) travels with every forward, so with windows it acts inside each window's.
         pag: None, or the layers of perturbed-attention guidance: one more replica, the last, runs those context blocks with
         identity self-attention (apply_model*'s 'pag' = (layers, first perturbed row)); with windows, in each window's forward.
+        Or the dict of _pert_fwd (smoothed energy guidance): the same replica blurs its queries in those blocks instead
+        (apply_model*'s 'seg' = (layers, first perturbed row, sigma) and 'seg_buffers' = (taps, workspace)).
         x_info['tome_ratio'] / ['tome_max_downsample'] (token merging, vd._tome_arg) travel with every forward as apply_model*'s
         'tome', so with windows the merge acts on each window's token grid.
         x_info['hypertile'] / ['hypertile_max_downsample'] (HyperTile, vd._hypertile_arg) travel the same way, as apply_model*'s
@@ -606,7 +615,11 @@ class DDIMSampler(object):
         xi = {"type": x_info["type"], "x": x, "repeat": reps}
         if pag is not None:
             assert deep is None, "DeepCache does not combine with pag"
-            xi["pag"] = (pag, (reps - 1) * x.shape[0])
+            if isinstance(pag, dict):
+                xi["seg"] = (pag["layers"], (reps - 1) * x.shape[0], pag["sigma"])
+                xi["seg_buffers"] = (pag["taps"], pag["qb"])
+            else:
+                xi["pag"] = (pag, (reps - 1) * x.shape[0])
         if sag is not None:
             assert deep is None, "DeepCache does not combine with sag"
             xi["sag"] = sag
@@ -625,6 +638,29 @@ class DDIMSampler(object):
         if single:
             return self.model.apply_model(xi, t, c_info_list[0])
         return self.model.apply_model_multicontext(xi, t, c_info_list)
+
+    @staticmethod
+    def _pert_fwd(pag, device, st=None):
+        """What _eps takes as `pag`: the layers of perturbed-attention guidance (pag = (s_pag, layers)), or for smoothed energy
+        guidance (pag = (s_seg, layers, sigma)) the dict {"layers", "sigma", "taps", "qb"} -- taps and workspace from the static
+        state `st` (a captured step uploads and allocates nothing), else the taps uploaded here and no workspace (every launch
+        allocates its own)."""
+        if len(pag) == 2:
+            return pag[1]
+        if st is not None:
+            return {"layers": pag[1], "sigma": pag[2], "taps": st["seg_taps"], "qb": st["seg_qb"]}
+        taps = seg_taps(pag[2])[1]
+        return {"layers": pag[1], "sigma": pag[2], "taps": None if taps is None else torch.from_numpy(taps).to(device), "qb": None}
+
+    def _seg_state_arg(self, pag, x, c_info_list, window):
+        """_new_state's `pag` of a call: False, True (perturbed-attention guidance), or for smoothed energy guidance the dict
+        {"R", "rows", "elems", "types"}: the tap radius (-1: mean mode), the rows of the perturbed replica in a forward, the fp16
+        elements one of them needs at most (vd.seg_workspace_elems on the latent or the window) and the number of context types."""
+        if pag is None or len(pag) == 2:
+            return pag is not None
+        H, W = (x.shape[2], x.shape[3]) if window is None else window["key"][:2]
+        return {"R": seg_taps(pag[2])[0], "rows": x.shape[0] * (1 if window is None else window["m"]),
+                "elems": seg_workspace_elems(self.model, [ci["type"] for ci in c_info_list], H, W, pag[1]), "types": len(c_info_list)}
 
     def _sag_eager(self, sag, scale, guided, c_info_list, x):
         """The device state of self-attention guidance for one call of the eager loop (or one p_sample_ddim*): what _new_state keeps
@@ -684,7 +720,9 @@ class DDIMSampler(object):
         window (the plan of _window_args): "window" holds its tables and buffers (_window_state), and "ts" has a row per
         window slot like the context batches.  pag (perturbed-attention guidance on): "ts" and the window buffers have the rows
         of replica_count(guided, pag) replicas, and "pag_w" is the fold's weight (fp32 [1], loaded per call: one graph serves
-        every positive pag_scale and every guidance scale).  sag (self-attention guidance on): "sag" holds the buffers of
+        every positive pag_scale and every guidance scale); a dict (_seg_state_arg: smoothed energy guidance, the same replica and
+        fold) adds "seg_taps" (fp32 [2 R + 1], loaded per call: one graph serves every sigma of the same R; None in mean mode) and
+        "seg_qb" (fp16 [context types, perturbed rows, elements]: the workspace of the blurred queries).  sag (self-attention guidance on): "sag" holds the buffers of
         _sag_buffers; its weight, taps and ratios are loaded per call, its coefficients per step: one graph serves every sag_scale,
         sigma and guidance scale.  apg (adaptive projected guidance on): "apg_v" is the running direction (fp32, like the latent),
         "apg_coef" the fold's row (fp32 [8], loaded per step) and "apg_fac" its per-sample figures (fp32 [B, 4], written by every
@@ -702,6 +740,9 @@ class DDIMSampler(object):
             st["window"] = self._window_state(window, x, guided, pag)
         if pag:
             st["pag_w"] = torch.empty((1,), device=x.device, dtype=torch.float32)
+        if isinstance(pag, dict):
+            st["seg_taps"] = None if pag["R"] < 0 else torch.empty((2 * pag["R"] + 1,), device=x.device, dtype=torch.float32)
+            st["seg_qb"] = torch.empty((pag["types"], pag["rows"], pag["elems"]), device=x.device, dtype=torch.float16)
         if sag:
             st["sag"] = self._sag_buffers(x, len(c_info_list))
         if apg:
@@ -745,7 +786,10 @@ class DDIMSampler(object):
         # is off: the tile side is an argument of the captured tile / untile launches and decides the attention's shapes;
         # and adaptive projected guidance, likewise: a further entry ("apg",) at the very end when it is on (a guided call whose
         # triple is not the neutral one), nothing when it is off: a graph captured with it launches the fold; eta, threshold and
-        # momentum are not in the key -- the fold's row is loaded per step)
+        # momentum are not in the key -- the fold's row is loaded per step;
+        # and smoothed energy guidance, likewise: a further entry ("seg", layers, R) when it is on, R = -1 for the mean query: a graph
+        # captured with it runs pag's extra replica with the query blur of those blocks at that tap radius and the fold; its scale
+        # and its taps are not in the key -- both are loaded per call, so one graph serves every sigma of the same R)
         pag = _pag_arg(x_info, self.model)
         tome = _tome_arg(x_info, self.model)
         mask_batch = 0 if inpaint is None else inpaint["mask"].shape[0]
@@ -760,6 +804,9 @@ class DDIMSampler(object):
             key = key + (("sag",),)
         if guided and _apg_arg(x_info) is not None:
             key = key + (("apg",),)
+        seg = _seg_arg(x_info, self.model)
+        if seg is not None:
+            key = key + (("seg", seg[1], seg_taps(seg[2])[0]),)
         return key
 
     def _static_state(self, x, x_info, c_info_list, guided, single, inpaint=None, rescale=0., cache_depth=0, window=None, pag=False,
@@ -778,8 +825,8 @@ class DDIMSampler(object):
         self._static[key] = st                                 # most recently used last
         return st
 
-    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None, sag=None):
-        """Copy this call's latent, contexts, inpainting tensors, region masks (with their inv_den; `window` is the call's
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None, sag=None, seg=None):
+        """seg: None, or the fp32 taps of this call's smoothed energy guidance (vd.seg_taps), copied into "seg_taps".  Copy this call's latent, contexts, inpainting tensors, region masks (with their inv_den; `window` is the call's
         plan), the weight of the perturbed-attention fold (pag_w, pag_weight) and the weight, taps and ratios of self-attention
         guidance (sag = (s_sag, sigma, guidance scale, guided); _sag_load) into the state and hand its context buffers and
         K/V caches to c_info_list.  Returns whether step 0 may be replayed (else it runs eagerly and refreshes the K/V on its way)."""
@@ -791,6 +838,8 @@ class DDIMSampler(object):
             st["phi"].fill_(phi)
         if "pag_w" in st:
             st["pag_w"].fill_(float(pag_w))
+        if st.get("seg_taps") is not None:
+            st["seg_taps"].copy_(torch.from_numpy(seg))
         if "sag" in st:
             self._sag_load(st["sag"], sag[:2], sag[2], sag[3], c_info_list)
         if inpaint is not None:
@@ -842,7 +891,8 @@ class DDIMSampler(object):
         every cache either walk needs (the shallow walk runs a subset of the full walk's blocks at the same shapes).
         window (the plan of _window_args): the step's prediction is the fusion of the windows' (_eps_windowed); the update, the
         rescale factors, the blend, the seeded noise and the solver histories see the canvas and nothing else.
-        pag (None, or (s_pag, layers) of vd._pag_arg): the forward runs one more replica, perturbed, and ops.pag_fold folds its
+        pag (None, or (s_pag, layers) of vd._pag_arg, or (s_seg, layers, sigma) of vd._seg_arg -- smoothed energy guidance, the same
+        replica with blurred queries instead of the identity map): the forward runs one more replica, perturbed, and ops.pag_fold folds its
         prediction into replica 0 between the forward and the update; the update, the rescale factors, the blend, the noise and the
         histories see the folded pair (or single) and nothing else, so every sampler on this loop gets it.
         sag (None, or (s_sag, sigma) of vd._sag_arg): the step runs TWO forwards in sequence in the one captured graph -- the first,
@@ -859,13 +909,16 @@ class DDIMSampler(object):
         total_steps = timesteps.shape[0]
         rescale = phi if guided else 0.          # the guidance-rescale weight of this call; 0: off
         cache_depth = depth if interval > 1 else 0
-        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pag is not None,
+        pstate = self._seg_state_arg(pag, x, c_info_list, window)     # False, True, or the sizes of smoothed energy guidance
+        st = (self._static_state(x, x_info, c_info_list, guided, single, inpaint, rescale, cache_depth, window, pstate,
                                  sag is not None, apg is not None)
-              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pag is not None, sag is not None,
+              or self._new_state(x, c_info_list, guided, inpaint, rescale, cache_depth, window, pstate, sag is not None,
                                  apg is not None))
         replay_first = self._load_state(st, x, c_info_list, inpaint, rescale, window,
                                         None if pag is None else pag_weight(scale, pag[0], guided),
-                                        None if sag is None else (sag[0], sag[1], scale, guided))
+                                        None if sag is None else (sag[0], sag[1], scale, guided),
+                                        seg_taps(pag[2])[1] if isinstance(pstate, dict) else None)
+        pfwd = None if pag is None else self._pert_fwd(pag, x.device, st)
         sag_tab = None if sag is None else torch.from_numpy(sag_coef_table(self.alphas_cumprod, timesteps[:total_steps])).to(x.device)
         apg_tab = None if apg is None else torch.from_numpy(apg_coef_table(self.alphas_cumprod, timesteps[:total_steps], *apg)).to(x.device)
         per_sample = x.numel() // x.shape[0]
@@ -877,7 +930,7 @@ class DDIMSampler(object):
 
         def body(mode=None):
             eps = self._eps(x_info, st["xs"], st["ts"], c_info_list, guided, single, emb_rows,
-                            None if mode is None else (st["deep"], mode), st.get("window"), None if pag is None else pag[1],
+                            None if mode is None else (st["deep"], mode), st.get("window"), pfwd,
                             None if sag is None else st["sag"]["mass"])
             eps = eps.contiguous()
             if apg is not None:     # replica 0 rewritten from the latent, the pair and the running direction
@@ -1064,6 +1117,9 @@ class DDIMSampler(object):
             raise ValueError("window: windowed sampling runs whole sample() loops; p_sample_ddim* fuses no windows (or regions)")
         _freeu_arg(x_info)      # FreeU is stateless: the step's forward applies it (_eps)
         pag = _pag_arg(x_info, self.model)      # so is perturbed-attention guidance: one more replica and the fold
+        seg = _seg_arg(x_info, self.model, x_info["x"].shape)   # and smoothed energy guidance: the same replica, blurred queries
+        if seg is not None:
+            pag = seg
         _tome_arg(x_info, self.model, x_info["x"].shape)    # and token merging: the step's forward applies it (_eps)
         _hypertile_arg(x_info, self.model, x_info["x"].shape)   # and HyperTile: the step's forward applies it (_eps)
         sag = _sag_arg(x_info, self.model, x_info["x"].shape)   # and self-attention guidance: the step runs its second forward
@@ -1074,7 +1130,8 @@ class DDIMSampler(object):
             raise ValueError("apg: adaptive projected guidance runs whole sample() loops; p_sample_ddim* keeps no direction between steps")
         x = x_info["x"]
         if pag is not None:
-            pag = (pag[1], torch.full((1,), float(pag_weight(scale, pag[0], guided)), device=x.device, dtype=torch.float32))
+            pag = (self._pert_fwd(pag, x.device),
+                   torch.full((1,), float(pag_weight(scale, pag[0], guided)), device=x.device, dtype=torch.float32))
         x16 = x.to(torch.float16).contiguous()
         xp, p0, _ = self._step(x16, x_info, cis, int(t[0]), index, guided, scale,
                                temperature, single, noise_dropout=noise_dropout,

@@ -246,12 +246,12 @@ class DPMSolverSDESampler(DPMSolverSampler):
         return dict(super()._extra_static(x), seeds=torch.zeros((x.shape[0],), device=x.device, dtype=torch.int64),
                     rng=torch.zeros((2,), device=x.device, dtype=torch.int32))
 
-    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None, sag=None):
+    def _load_state(self, st, x, c_info_list, inpaint, phi=0., window=None, pag_w=None, sag=None, seg=None):
         if self._seeds is None:
             st["seeds"].zero_()          # eta = 0 without seeds: the noise coefficient is 0 and the seeds are not read
         else:
             st["seeds"].copy_(self._seeds)
-        return super()._load_state(st, x, c_info_list, inpaint, phi, window, pag_w, sag)
+        return super()._load_state(st, x, c_info_list, inpaint, phi, window, pag_w, sag, seg)
 
     def _solver_update(self, bufs, eps, guided):
         if "kfac" in bufs:

@@ -99,7 +99,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
                       window_weight="uniform", window_batch=8, freeu=None, region_masks=None, pag_scale=None,
                       pag_layers=None, tome_ratio=None, tome_max_downsample=None, vae_tile=None, vae_tile_stride=None,
                       vae_tile_wrap=None, vae_tile_weight=None, vae_tile_batch=None, sag_scale=None, sag_blur_sigma=None,
-                      hypertile=None, hypertile_max_downsample=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None):
+                      hypertile=None, hypertile_max_downsample=None, apg_eta=None, apg_norm_threshold=None, apg_momentum=None,
+                      seg_scale=None, seg_blur_sigma=None, seg_layers=None):
     """t2i / image-variation / multi-context sampling + kl-f8 decode of a full batch, sharded over the process group.
 
     images + fidelity > 0: image variation with fidelity (reference app.py:355-371) -- `images` is THIS RANK's slice of
@@ -136,6 +137,9 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
 
     hypertile, hypertile_max_downsample: the samplers' x_info['hypertile'] and x_info['hypertile_max_downsample'] (HyperTile,
     vd._hypertile_arg; None = the key is not set).  The tiles are cut per sample, so a rank's slice sees what the whole batch would.
+
+    seg_scale, seg_blur_sigma, seg_layers: the samplers' x_info keys of the same names (smoothed energy guidance, vd._seg_arg; None =
+    the key is not set).  The perturbed replica and its query blur are per sample, so a rank's slice sees what the whole batch would.
 
     apg_eta, apg_norm_threshold, apg_momentum: the samplers' x_info keys of the same names (adaptive projected guidance,
     vd._apg_arg; None = the key is not set).  The projection, the norm and the running direction are per sample, so a rank's slice
@@ -203,7 +207,8 @@ def vd_sample_sharded(net, sampler, steps, shape, c_info_list, seed, guidance_sc
             x_info["hypertile"] = hypertile
         if hypertile_max_downsample is not None:
             x_info["hypertile_max_downsample"] = hypertile_max_downsample
-        for key, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum)):
+        for key, value in (("apg_eta", apg_eta), ("apg_norm_threshold", apg_norm_threshold), ("apg_momentum", apg_momentum),
+                           ("seg_scale", seg_scale), ("seg_blur_sigma", seg_blur_sigma), ("seg_layers", seg_layers)):
             if value is not None:
                 x_info[key] = value
         from .dpm_solver import DPMSolverSDESampler

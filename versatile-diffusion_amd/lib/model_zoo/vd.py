@@ -400,6 +400,163 @@ def _pag_fwd_arg(x_info, net):
     return pag_layers(pag[0], net), int(row0)
 
 
+# ---- smoothed energy guidance (x_info['seg_scale'], ['seg_blur_sigma'], ['seg_layers']; forward key x_info['seg']) ---------------
+# Hong, "Smoothed Energy Guidance: Guiding Diffusion Models with Reduced Energy Curvature of Attention" (NeurIPS 2024); ComfyUI's SEG
+# node and diffusers' SmoothedEnergyGuidance.  The perturbed replica of perturbed-attention guidance, with a milder perturbation: the
+# chosen context blocks keep their softmax and Gaussian-blur the replica's queries over the token grid (run_unet(seg=...),
+# ops.attention(blur_from=...), contract in include/vd_hip.h).  The samplers fold its prediction with ops.pag_fold, like pag's.
+SEG_DEFAULT_SCALE = 3.0         # the upstream default of seg_scale (the key itself defaults to off)
+SEG_MEAN_SIGMA = 9999.0         # from here on (the upstream rule), and at math.inf, every query becomes the sample's mean query
+
+
+def seg_taps(sigma):
+    """(R, taps) of x_info['seg_blur_sigma']: (-1, None) in mean mode (sigma >= 9999 or infinite); else ks = ceil(6 sigma), made odd by
+    adding 1, R = (ks - 1) / 2 and taps = fp32 [2 R + 1], w[d] = exp(-0.5 (d / sigma)^2) normalised to sum 1 in float64 and rounded
+    once.  ValueError (matching 'seg') for a sigma that is no real number, NaN, not > 0, or so small that R < 1."""
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or np.isnan(float(sigma)) \
+            or not float(sigma) > 0.:
+        raise ValueError("x_info['seg_blur_sigma'] (seg) must be a real number > 0 or math.inf, got %r" % (sigma,))
+    sigma = float(sigma)
+    if np.isinf(sigma) or sigma >= SEG_MEAN_SIGMA:
+        return -1, None
+    ks = int(np.ceil(6.0 * sigma))
+    ks += 1 - ks % 2
+    R = (ks - 1) // 2
+    if R < 1:
+        raise ValueError("x_info['seg_blur_sigma'] (seg) = %r leaves a single tap: ceil(6 sigma) must be >= 2" % (sigma,))
+    w = np.exp(-0.5 * (np.arange(-R, R + 1, dtype=np.float64) / sigma) ** 2)
+    return R, (w / w.sum()).astype(np.float32)
+
+
+def seg_refl(i, n):
+    """Reflection without repeating the edge (torch's 'reflect' padding), folded as often as needed (period 2 (n - 1)); 0 for n == 1."""
+    if n == 1:
+        return 0
+    p = 2 * (n - 1)
+    i %= p
+    return i if i < n else p - i
+
+
+def seg_grids(net, H0, W0):
+    """[(H, W)] per context block of the 2-D data net `net` in walk order on an H0 x W0 latent: every Downsample halves a side,
+    rounding up, the way up returns to the sizes of the way down."""
+    from .openaimodel import Downsample, Upsample
+    pag_context_blocks(net)
+    d_iter = iter(net.data_blocks)
+    sizes = [(int(H0), int(W0))]
+    level, out = 0, []
+    for s in list(net.i_order) + list(net.m_order) + list(net.o_order):
+        if s == "d":
+            blk = next(d_iter)
+            if any(isinstance(m, Downsample) for m in blk.modules()):
+                level += 1
+                if level == len(sizes):
+                    sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+            elif any(isinstance(m, Upsample) for m in blk.modules()):
+                level -= 1
+        elif s == "c":
+            out.append(sizes[level])
+    return out
+
+
+def seg_workspace_elems(model, c_types, H0, W0, layers):
+    """The fp16 elements one perturbed sample's blurred queries take at most in the context blocks `layers` (walk indices) of the
+    image flow on an H0 x W0 latent (or window): max H W C over those blocks and the context types `c_types`."""
+    grids = seg_grids(model.diffuser["image"], H0, W0)
+    need = 0
+    for ct in c_types:
+        blocks = list(model.diffuser[ct].context_blocks)
+        for ci in layers:
+            st = blocks[ci]
+            st = st[0] if isinstance(st, (nn.Sequential, list, tuple)) else st
+            need = max(need, grids[ci][0] * grids[ci][1] * int(st.proj_in.out_channels))
+    return need
+
+
+def _seg_arg(x_info, model, shape=None):
+    """The sampler keys of smoothed energy guidance validated: None when x_info['seg_scale'] is absent, None or 0 (off: today's call,
+    the other keys are then ignored), else (s_seg as a float, the layers of x_info['seg_layers'] -- pag_layers' values and validator,
+    default "mid" -- and sigma = x_info['seg_blur_sigma'], default math.inf) on the 2-D image flow; 3.0 is the upstream default of
+    the scale.  ValueError (matching 'seg') for a scale that is no real number, negative or not finite, a bad sigma (seg_taps), bad
+    layers, another flow, and for the combinations left out of scope on purpose: pag_scale or sag_scale (one replica-0 fold per
+    step), tome_ratio (the token grid is gone), cache_interval > 1 and region_masks (as pag), and, when `shape` ([B, C, H, W]) is
+    given, a chosen layer that HyperTile tiles.  Touches no device."""
+    value = x_info.get("seg_scale")
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(float(value)) or float(value) < 0.:
+        raise ValueError("x_info['seg_scale'] must be a finite real number >= 0, got %r" % (value,))
+    if float(value) == 0.:
+        return None
+    sigma = x_info.get("seg_blur_sigma")
+    sigma = float("inf") if sigma is None else sigma
+    seg_taps(sigma)
+    if x_info.get("type") != "image":
+        raise ValueError("seg_scale applies to x_info['type'] == 'image' only (blurred self-attention queries of the 2-D net), got %r"
+                         % (x_info.get("type"),))
+    if x_info.get("pag_scale") not in (None, 0, 0.) or x_info.get("pag") is not None:
+        raise ValueError("seg_scale with pag_scale is out of scope on purpose: one replica-0 fold per step")
+    if x_info.get("sag_scale") not in (None, 0, 0.) or x_info.get("sag") is not None:
+        raise ValueError("seg_scale with sag_scale is out of scope on purpose: one replica-0 fold per step")
+    if x_info.get("tome_ratio") not in (None, 0, 0.) or x_info.get("tome") is not None:
+        raise ValueError("seg_scale with tome_ratio is out of scope on purpose: merged tokens have no grid to blur over")
+    cache = x_info.get("cache_interval", 1)
+    if not isinstance(cache, (bool, str)) and isinstance(cache, (int, np.integer)) and cache > 1:
+        raise ValueError("seg_scale with cache_interval > 1 is out of scope on purpose: DeepCache and seg do not combine")
+    if x_info.get("region_masks") is not None:
+        raise ValueError("seg_scale with region_masks is out of scope on purpose: regional prompts and seg do not combine")
+    net = model.diffuser[x_info["type"]]
+    try:
+        layers = pag_layers(x_info.get("seg_layers"), net)
+    except ValueError as e:
+        raise ValueError(str(e).replace("pag_layers", "seg_layers").replace("pag", "seg")) from None
+    if shape is not None and x_info.get("hypertile") is not None:
+        ht = _hypertile_arg(x_info, model, shape)
+        if ht is not None:
+            H, W = int(shape[2]), int(shape[3])
+            if x_info.get("window") is not None:
+                from . import windows
+                h, w = windows.int_pair("window", x_info["window"])
+                H, W = min(h, H), min(w, W)
+            tiled = {b[0] for b in hypertile_blocks(net, H, W, ht)}
+            if tiled & set(layers):
+                raise ValueError("seg_layers %r: HyperTile tiles the context block(s) %r, whose queries seg would blur over the whole "
+                                 "grid: lower hypertile_max_downsample or choose other layers" % (layers, sorted(tiled & set(layers))))
+    return float(value), layers, float(sigma)
+
+
+def _seg_fwd_arg(x_info, net, device):
+    """x_info['seg'] (extension key of apply_model*, set by the samplers) validated: None, or (layers, row0, taps, R, qb) for
+    run_unet -- x_info['seg'] = (layers, row0, sigma): the rows >= row0 of the batch, counted after replication, blur their
+    self-attention queries with seg_taps(sigma) in the context blocks `layers` (pag_layers) of `net`.  x_info['seg_buffers'] =
+    (taps, qb), when present (a captured step: nothing is uploaded or allocated then), are the device fp32 taps (None in mean mode)
+    and the fp16 workspace [context types, perturbed rows, seg_workspace_elems]; else the taps are uploaded here."""
+    seg = x_info.get("seg")
+    if seg is None:
+        return None
+    if x_info.get("type") != "image":
+        raise ValueError("seg applies to x_info['type'] == 'image' only, got %r" % (x_info.get("type"),))
+    if not (isinstance(seg, (tuple, list)) and len(seg) == 3):
+        raise ValueError("x_info['seg'] must be (layers, row0, sigma), got %r" % (seg,))
+    if x_info.get("pag") is not None or x_info.get("sag") is not None or x_info.get("tome") is not None:
+        raise ValueError("seg with pag, sag or tome in the same forward is out of scope on purpose")
+    row0 = seg[1]
+    if isinstance(row0, (bool, np.bool_)) or not isinstance(row0, (int, np.integer)) or row0 < 0:
+        raise ValueError("x_info['seg']: row0 must be an int >= 0, got %r" % (row0,))
+    try:
+        layers = pag_layers(seg[0], net)
+    except ValueError as e:
+        raise ValueError(str(e).replace("pag_layers", "seg_layers").replace("pag", "seg")) from None
+    R, taps = seg_taps(seg[2])
+    bufs = x_info.get("seg_buffers")
+    if bufs is not None:
+        taps_dev, qb = bufs
+    else:
+        taps_dev, qb = (None if taps is None else torch.from_numpy(taps).to(device)), None
+    return layers, int(row0), taps_dev, R, qb
+
+
 # ---- token merging (x_info['tome_ratio'], x_info['tome_max_downsample']; forward key x_info['tome']) ---------------------------
 # Bolya & Hoffman, "Token Merging for Fast Stable Diffusion" (2023); tomesd.apply_patch(model, ratio, max_downsample) with
 # sx = sy = 2 and use_rand = False.  In the context blocks whose token grid is the latent grid (or, max_downsample = 2, half of it
@@ -776,7 +933,7 @@ def kv_rows(cache, rows):
 
 
 def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1, emb_rows=None, deep=None, freeu=None, pag=None,
-             tome=None, sag=None, hypertile=None):
+             tome=None, sag=None, hypertile=None, seg=None):
     """Walk i/m/o orders of `data_net` (reference vd.py:352-378 / 429-453).
 
     ctx_specs: list of (context_blocks, context [B, L, Dc], ratio, kv_cache or None), one per context type.
@@ -814,7 +971,23 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     their self-attention inside square tiles of their token grid (SpatialTransformer.forward(tile=(side, side))), the block that
     takes a guided batch un-replicated too.  Every other block, and a forward without it, keeps today's launches and bits.  It
     combines with pag (a perturbed layer that is tiled keeps its identity rows), deep and freeu; not with tome, nor with a sag whose
-    map block is tiled (ValueError)."""
+    map block is tiled (ValueError).
+    seg: None, or (layers, row0, taps, R, qb) of _seg_fwd_arg: pag's walk with another perturbation -- in the context blocks whose
+    walk index is in `layers` the rows >= row0 blur their self-attention queries over the block's token grid
+    (SpatialTransformer.forward(blur_from=..., blur=(taps, R[, qb]))), a half-batch branch gets the clamped index, h is replicated in
+    front of the first context block.  qb: None (every call allocates its workspace), or fp16 [context types, perturbed rows, *]:
+    type t's module writes the blurred queries of the perturbed rows [p0, p1) it holds into qb[t, p0:p1], so forked branches and
+    forked context types never share a byte.  It does not combine with pag, tome, sag, deep or a tiled chosen layer (ValueError)."""
+    if seg is not None:
+        if x.dim() != 4:
+            raise ValueError("seg needs a 2-D data net (x_info['type'] == 'image')")
+        if pag is not None or tome is not None or sag is not None or deep is not None:
+            raise ValueError("seg does not combine with pag, tome, sag or deep_cache")
+        if not 0 <= seg[1] <= repeat * x.shape[0]:
+            raise ValueError("seg: row0 = %d is outside the batch of %d x %d rows" % (seg[1], repeat, x.shape[0]))
+        if seg[4] is not None and (seg[4].dim() != 3 or seg[4].shape[0] < len(ctx_specs) or seg[4].shape[1] < repeat * x.shape[0] - seg[1]):
+            raise ValueError("seg: the workspace %s is not [>= %d context types, >= %d perturbed rows, *]"
+                             % (tuple(seg[4].shape), len(ctx_specs), repeat * x.shape[0] - seg[1]))
     hmap = None
     if hypertile is not None:
         if x.dim() != 4:
@@ -824,6 +997,8 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
         hmap = {b[0] for b in hypertile_blocks(data_net, x.shape[-2], x.shape[-1], hypertile)}
         if sag is not None and pag_context_blocks(data_net)[1] in hmap:
             raise ValueError("hypertile would tile the block sag reads its map from")
+        if seg is not None and hmap & set(seg[0]):
+            raise ValueError("seg: hypertile tiles the chosen context block(s) %r" % (sorted(hmap & set(seg[0])),))
         hmap = (hmap, (hypertile.tile, hypertile.tile)) if hmap else None
     smap = None
     if sag is not None:
@@ -898,13 +1073,15 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     def context_kv(module, spec):
         return kv_lookup(spec[3], module, spec[1])
 
-    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None):
+    def run_context(h, modules, specs, rs, sl=None, repeat=1, ident_from=None, tome=None, sag=None, tile=None, blur=None):
         """sl = (b0, b1): h holds samples b0 .. b1 - 1 of the batch (a half-batch branch): contexts and K/V are sliced alike.
         repeat > 1 (one context type, whole batch): h holds one replica, the block returns all of them.
         ident_from: None, or the first row of h that takes identity self-attention in these blocks (pag).
         tome: None, or (r, sink) of token merging for these blocks' self-attention.
         sag: None, or the mass buffer [T, B, Nm] of self-attention guidance: module t writes the rows of replica 0 that h holds.
-        tile: None, or (th, tw) of HyperTile for these blocks' self-attention."""
+        tile: None, or (th, tw) of HyperTile for these blocks' self-attention.
+        blur: None, or (blur_from, p0, taps, R, qb) of smoothed energy guidance: the rows of h from blur_from on blur their queries in
+        these blocks; they are the perturbed rows p0 ... of the batch, and module t's workspace is qb[t, p0:p0 + their count]."""
         single = len(modules) == 1
         pkw = {} if ident_from is None else {"ident_from": int(ident_from)}
         if tome is not None:
@@ -912,6 +1089,12 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
         if tile is not None:
             pkw["tile"] = tile
         skw = [{} for _ in modules]
+        if blur is not None:
+            assert repeat == 1
+            bf, p0, taps, R, qb = blur
+            cnt = h.shape[0] - bf
+            skw = [{"blur_from": int(bf), "blur": (taps, R) + (() if qb is None or cnt <= 0 else (qb[t, p0:p0 + cnt].reshape(-1),))}
+                   for t in range(len(modules))]
         if sag is not None:
             lo, hi = (0, sag.shape[1]) if sl is None else (sl[0], min(sl[1], sag.shape[1]))
             if hi > lo:
@@ -977,7 +1160,7 @@ def run_unet(data_net, ctx_specs, x, emb_silu, mixing_type="attention", repeat=1
     try:
         return _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, lambda ms, sps: [context_kv(m, sp) for m, sp in zip(ms, sps)],
                               h, nb, shared, repeat, None if deep is None else (deep[0], deep[1], cut, (id(data_net), deep[0].depth)),
-                              fmap or None, pag, tmap, smap, hmap)
+                              fmap or None, pag, tmap, smap, hmap, seg)
     finally:
         arena.end()
         data_net.__dict__[need_key] = arena.need
@@ -1018,8 +1201,8 @@ def _fork_region(steps, hw0, thr):
 
 
 def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_context, h, nb, shared, repeat, deep=None, fmap=None,
-                   pag=None, tome=None, sag=None, hypertile=None):
-    """hypertile: None, or ({walk index of a tiled context block}, (th, tw)) of run_unet.  sag: None, or (walk index of the middle stage's first context block, the mass buffer) of run_unet.  deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
+                   pag=None, tome=None, sag=None, hypertile=None, seg=None):
+    """seg: None, or (layers, row0, taps, R, qb) of run_unet.  hypertile: None, or ({walk index of a tiled context block}, (th, tw)) of run_unet.  sag: None, or (walk index of the middle stage's first context block, the mass buffer) of run_unet.  deep: None, or (DeepCache, mode, (a, b), key) of run_unet's cached walk.  fmap: None, or {width of the entering h: (b, s)} of
     the active FreeU stages.  pag: None, or (layers, row0) of run_unet.  tome: None, or ({walk index of a merging context block: r},
     the TokenMerge's record list or None)."""
     state = {"shared": shared}
@@ -1043,7 +1226,7 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 if state["shared"]:  # the replicas diverge here
                     rep = lambda t: ops.repeat_batch(t, repeat)   # per-channel statistics of the tensors travel along
                     hs[:] = [rep(t) for t in hs]
-                    if CFG_HEAD_SHARE and pag is None and len(st[1]) == 1 and sl is None and h.dim() == 4 and _shares_cfg_head(st[1][0]):
+                    if CFG_HEAD_SHARE and pag is None and seg is None and len(st[1]) == 1 and sl is None and h.dim() == 4 and _shares_cfg_head(st[1][0]):
                         share = repeat   # ... inside the block, behind its self-attention: h goes in un-replicated
                     else:
                         h = rep(h)
@@ -1052,6 +1235,10 @@ def _run_unet_body(steps, emb_outs, emb_rows, emb_silu, run_context, prepare_con
                 if pag is not None and st[4] in pag[0]:
                     b0, b1 = (0, h.shape[0]) if sl is None else sl
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, ident_from=min(max(pag[1] - b0, 0), b1 - b0), **tkw)
+                elif seg is not None and st[4] in seg[0]:
+                    b0, b1 = (0, h.shape[0]) if sl is None else sl
+                    bf = min(max(seg[1] - b0, 0), b1 - b0)
+                    h = run_context(h, st[1], st[2], st[3], sl, repeat=share, blur=(bf, b0 + bf - seg[1], seg[2], seg[3], seg[4]))
                 elif tome is not None and st[4] in tome[0]:
                     sink = None if tome[1] is None else (lambda row_of, ci=st[4], rec=tome[1]: rec.append((ci, row_of.clone())))
                     h = run_context(h, st[1], st[2], st[3], sl, repeat=share, tome=(tome[0][st[4]], sink))
@@ -1288,6 +1475,7 @@ class VD_v2_0(nn.Module):
         deep = _deep_arg(x_info)        # extension key: (DeepCache, "store" | "reuse"), see run_unet
         freeu = _freeu_arg(x_info)      # extension key: (b1, b2, s1, s2), see run_unet
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])   # extension key: (layers, row0), see run_unet
+        seg = _seg_fwd_arg(x_info, self.diffuser[x_type], x.device)   # extension key: (layers, row0, sigma), see run_unet
         tome = _tome_fwd_arg(x_info)    # extension key: a TokenMerge, see run_unet
         hypertile = _hypertile_fwd_arg(x_info)      # extension key: a HyperTile, see run_unet
         sag = _sag_fwd_arg(x_info, 1)   # extension key: the fp32 [1, B, Nm] mass buffer of self-attention guidance, see run_unet
@@ -1295,7 +1483,7 @@ class VD_v2_0(nn.Module):
         spec = (self.diffuser[c_type].context_blocks, self._prep(c), 1.0, c_info.get("kv_cache"))
         return run_unet(self.diffuser[x_type], [spec], self._prep(x), emb, repeat=int(x_info.get("repeat", 1)),
                         emb_rows=rows, deep=deep, freeu=freeu, pag=pag, tome=tome, sag=sag,
-                        hypertile=hypertile).to(x.dtype)
+                        hypertile=hypertile, seg=seg).to(x.dtype)
 
     @torch.no_grad()
     def apply_model_multicontext(self, x_info, timesteps, c_info_list, mixing_type="attention"):
@@ -1306,6 +1494,7 @@ class VD_v2_0(nn.Module):
         deep = _deep_arg(x_info)
         freeu = _freeu_arg(x_info)
         pag = _pag_fwd_arg(x_info, self.diffuser[x_type])
+        seg = _seg_fwd_arg(x_info, self.diffuser[x_type], x.device)
         tome = _tome_fwd_arg(x_info)
         hypertile = _hypertile_fwd_arg(x_info)
         sag = _sag_fwd_arg(x_info, len(c_info_list))
@@ -1315,4 +1504,4 @@ class VD_v2_0(nn.Module):
                  for ci in c_info_list]
         return run_unet(self.diffuser[x_type], specs, self._prep(x), emb, mixing_type,
                         repeat=int(x_info.get("repeat", 1)), emb_rows=rows, deep=deep, freeu=freeu, pag=pag,
-                        tome=tome, sag=sag, hypertile=hypertile).to(x.dtype)
+                        tome=tome, sag=sag, hypertile=hypertile, seg=seg).to(x.dtype)

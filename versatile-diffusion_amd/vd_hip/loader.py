@@ -130,6 +130,7 @@ PROTOTYPES = {
     "vd_freeu_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P]),
     "vd_attention_ident_f16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _F, _I, _I, _P]),
     "vd_pag_fold_f16": (_I, [_P, _L, _I, _P, _P]),
+    "vd_attention_qblur_f16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _F, _I, _I, _I, _I, _P, _I, _P, _P]),
     "vd_sag_mass_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _F, _P]),
     "vd_sag_degrade_f16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vd_sag_fold_f16": (_I, [_P, _P, _L, _P, _P]),

@@ -926,13 +926,20 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     return out
 
 
-def attention(q, k, v, heads, *, scale=None, causal=False, out=None, ident_from=None):
+def attention(q, k, v, heads, *, scale=None, causal=False, out=None, ident_from=None, blur_from=None, blur=None, qb=None):
     """q [B, Nq, *], k/v [B, Nk, *]: last-dim views (possibly column slices of a fused projection) with stride 1.
 
     Head h uses columns h*D:(h+1)*D of each.  Returns [B, Nq, heads*D] contiguous.
     ident_from (perturbed-attention guidance; None: the call above, unchanged): an int in [0, B]; the samples from it on take the
     identity attention map, out[b] = v[b] bit for bit, the samples in front of it the softmax path with the bits of a call on
-    them alone (vd_attention_ident_f16: self-attention without a causal mask only)."""
+    them alone (vd_attention_ident_f16: self-attention without a causal mask only).
+    blur_from, blur = (taps, R, gh, gw) (smoothed energy guidance; both None: the call above, unchanged; both or neither): blur_from
+    is an int in [0, B]; the samples from it on attend with their queries blurred over the gh x gw token grid (gh gw == Nq) by the
+    separable 2 R + 1 taps, a device fp32 tensor of at least that many elements -- or, R == -1, replaced by the sample's mean query
+    (taps may then be None) -- the samples in front of it the softmax path with the bits of a call on them alone
+    (vd_attention_qblur_f16: self-attention without a causal mask only; it does not combine with ident_from).  qb: the workspace
+    the blurred queries are written to, fp16 with at least (B - blur_from) Nq heads D elements, contiguous; None allocates one.  A
+    captured step hands in a buffer of its static state."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda or t.dtype != torch.float16 or t.stride(-1) != 1 or t.dim() != 3:
             raise VdHipError("%s must be a 3-d fp16 GPU tensor with unit inner stride" % n)
@@ -943,6 +950,36 @@ def attention(q, k, v, heads, *, scale=None, causal=False, out=None, ident_from=
         out = torch.empty((B, Nq, C), dtype=torch.float16, device=q.device)
     if scale is None:
         scale = D ** -0.5
+    if (blur_from is None) != (blur is None):
+        raise VdHipError("attention: blur_from and blur = (taps, R, gh, gw) go together, got %r and %r" % (blur_from, blur))
+    if blur_from is not None:
+        if ident_from is not None:
+            raise VdHipError("attention: blur_from does not combine with ident_from")
+        if isinstance(blur_from, bool) or not isinstance(blur_from, int):
+            raise VdHipError("blur_from must be None or an int in [0, %d], got %r" % (B, blur_from))
+        if not (isinstance(blur, (tuple, list)) and len(blur) == 4):
+            raise VdHipError("blur must be (taps, R, gh, gw), got %r" % (blur,))
+        taps, R, gh, gw = blur[0], int(blur[1]), int(blur[2]), int(blur[3])
+        if R >= 0:
+            if taps is None:
+                raise VdHipError("blur: R = %d needs the device taps, got None" % R)
+            _req(taps, "taps", torch.float32)
+            if taps.numel() < 2 * R + 1:
+                raise VdHipError("blur: taps holds %d elements, R = %d needs %d" % (taps.numel(), R, 2 * R + 1))
+        rows = max(B - min(max(blur_from, 0), B), 0)
+        if qb is None:
+            qb = torch.empty((max(rows, 1) * Nq * C,), dtype=torch.float16, device=q.device)
+        else:
+            _req(qb, "qb")
+            if qb.numel() < rows * Nq * C:
+                raise VdHipError("blur: the workspace qb holds %d elements, %d blurred samples need %d" % (qb.numel(), rows, rows * Nq * C))
+        with _Timed("attn_qblur<%d>" % D, 4.0 * B * Nq * Nk * C + 4.0 * rows * Nq * C * (2 * max(R, 0) + 1),
+                    2.0 * B * C * (2 * Nq + 2 * Nk) + 6.0 * rows * Nq * C):
+            _check(lib().vd_attention_qblur_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, heads, Nq, Nk, D, q.stride(1), k.stride(1),
+                                                v.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0),
+                                                float(scale), int(causal), blur_from, gh, gw, _ptr(taps) if R >= 0 else None, R,
+                                                _ptr(qb), _stream()))
+        return out
     if ident_from is not None:
         if isinstance(ident_from, bool) or not isinstance(ident_from, int):
             raise VdHipError("ident_from must be None or an int in [0, %d], got %r" % (B, ident_from))
